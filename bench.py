@@ -1,8 +1,15 @@
 """bench.py — frame-windows/sec (fwd+bwd) of the MultiDimStacker hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
       N > 1 without a torchrun environment: re-executes itself under
       `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU, RCCL).
+
+A plain run sets up, warms up, times the K steps and prints the result line (whole-path roofline fraction only).  --full adds
+what takes runs of its own: the per-kernel pass and its rocprofv3 child runs (`roofline` per kernel, `kernel_breakdown`,
+`top_launches`), `cpu_baseline`, `other_configs` and, for --config predict, the other predictor paths and precisions.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; the inputs are seeded, so two builds
+can be compared output for output): train / long004 `logits`, `loss`, `grads` (every trainable parameter's gradient, flat,
+in named_parameters order), `params` and `buffers` (after the optimizer step, flat); predict `probs` (the last frame's).
 
 Workloads (--config):
   train    BASELINE.json configs[1] (`sampling_weights_001`): per GPU a batch of 4 windows of 15x736x1280 synthetic
@@ -13,9 +20,10 @@ Workloads (--config):
            (forward only, BatchNorm in train mode), temporal tail forward+backward.
   predict  BASELINE.json configs[4] (src/predictors.py:50-75): sliding-window inference, one new 736x1280 frame per
            step (uint8 720x1280 ingest -> pad -> /255), frames/s, with and without horizontal-flip TTA.
-A step is one pass of the hot path over one batch; inputs are resident in HBM before the timed region.
+A step is one pass of the hot path over one batch; inputs are resident in HBM before the timed region.  A training step
+starts from the same weights every time (one device copy; the optimizer state carries on), so that runs repeat.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields plus, with --full,
   roofline     : the dominant HIP kernel family IN THE STEP (rocprofv3 --kernel-trace --stats child run of this very script,
                  both HIP streams running; fwd and bwd uses of one kernel folded together): algorithmic bytes (or flops)
                  per launch / its average in-step launch duration; `isolated` keeps the per-launch HIP-event numbers (each
@@ -64,6 +72,17 @@ def focal_loss(logits, target, gamma=1.2, alpha=-1.0):
     if alpha >= 0:
         loss = (alpha * target + (1 - alpha) * (1 - target)) * loss
     return loss.mean()
+
+
+def dump_outputs(d, tensors, limit=64 * 2**20):
+    """--dump-outputs: every tensor as float32 d/<name>.npy (at most `limit` bytes in all)."""
+    import numpy as np
+    arrays = {k: t.detach().float().cpu().numpy() for k, t in tensors.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= limit, f"--dump-outputs: {total} bytes > {limit}"
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def cpu_baseline(max_seconds=20.0, frames=15, frozen=False):
@@ -227,7 +246,7 @@ def trace_child(extra_args, steps=8, timeout=300):
 def other_config(name, extra, timeout=600):
     """One more BASELINE.json config measured by a child run of this script (fresh process: the 12 GB plan of the main
     workload is gone); returns its JSON line as a dict with the bulky per-kernel fields dropped."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--no-pmc", "--profile-steps", "0", "--no-other-configs", *extra]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--no-pmc", "--profile-steps", "0", "--no-other-configs", *extra]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -331,6 +350,7 @@ def bench_predict(args, dev, rank, world):
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         assert out is not None and torch.isfinite(out).all()
+        last["out"] = out
         return el
 
     def module_path(tta):      # round 1's path: forward_2d / forward_3d / forward_head module calls on padded fp32 frames
@@ -366,7 +386,7 @@ def bench_predict(args, dev, rank, world):
             print(json.dumps({"metric": "frames/sec, frame-by-frame API (trace child)", "value": round(K / el, 2), "unit": "frames/s"}))
         return
     fbf = None
-    if rank == 0 and world == 1:     # the plain calls first (a fresh process, as a caller of predict() has it)
+    if rank == 0 and world == 1 and args.full:     # the plain calls first (a fresh process, as a caller of predict() has it)
         fbf = {"note": "predict(frame, index) calls, each result consumed in order on the caller's stream (no look-ahead)",
                "fp32_frames_per_s": round(K / run(False, None, chunk=1), 1),
                "fp32_tta_frames_per_s": round(K / run(True, None, chunk=1), 1),
@@ -375,13 +395,15 @@ def bench_predict(args, dev, rank, world):
     L1 = args.lanes or 4          # lanes of the one-frame-per-pass runs
     el = run(False, None, pipelined=LN)
     lanes_in_use = getattr(last.get("sp"), "lanes_in_use", None)      # what the lane selection gave this process (mds.predict._lane_streams)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"probs": last["out"]})
     if world > 1:
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     fps = K * world / el
     extra = {}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         extra = {"fp32_tta_frames_per_s": round(K / run(True, None, pipelined=LN), 1), "bf16_frames_per_s": round(K / run(False, "bf16", pipelined=LN), 1),
                  "one_stream_no_lanes": {"note": f"predict_batch calls on the caller's stream, {CH} frames per call (rounds 2-4's headline path)",
                                          "fp32_frames_per_s": round(K / run(False, None), 1)},
@@ -487,7 +509,10 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--height", type=int, default=736)
     ap.add_argument("--width", type=int, default=1280)
-    ap.add_argument("--profile-steps", type=int, default=2)
+    ap.add_argument("--profile-steps", type=int, default=None, help="steps of the per-kernel pass (default 2 with --full, else 0)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: per-kernel pass, rocprofv3 child "
+                    "runs, cpu_baseline, other_configs, the other predictor paths (a plain run: only the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 child runs that measure roofline.traffic and the in-step kernel durations")
     ap.add_argument("--trace-only", action="store_true", help="with --no-pmc: still take the in-step kernel durations (rocprofv3 --kernel-trace "
@@ -506,6 +531,10 @@ def main():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 300 if args.config == "predict" else 20
+    if args.profile_steps is None:
+        args.profile_steps = 2 if args.full else 0
+    if not args.full:
+        args.no_cpu_baseline = args.no_pmc = args.no_other_configs = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn(args)
@@ -571,12 +600,31 @@ def main():
     target = torch.randint(0, 2, (B, 2), device=dev, generator=torch.Generator(dev).manual_seed(4321)).float()
     use_amp = args.dtype == "bf16"
 
+    last = {}
+    # every step starts from the same weights (the optimizer's moments carry on): the kernels sum gradients with float atomics,
+    # whose order varies from run to run in the last bits, and AdamW would carry that into the weights of every later step.  So
+    # each step is the same computation on the same inputs, and a run's outputs (--dump-outputs) repeat within rounding.
+    # The trainable weights move into one flat buffer (each tensor at a 512-byte boundary, as the caching allocator places them),
+    # so that the reset is a single copy launch.
+    offs, n = [], 0
+    for p in trainable:
+        offs.append(n); n += -(-p.numel() // 128) * 128
+    flat = torch.zeros(n, device=dev)
+    with torch.no_grad():
+        for p, o in zip(trainable, offs):
+            flat[o:o + p.numel()].copy_(p.reshape(-1))
+            p.data = flat[o:o + p.numel()].view_as(p)
+    start = flat.clone()
+
     def step():
+        flat.copy_(start)
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
-            loss = loss_fn(model(x), target)
+            logits = model(x)
+            loss = loss_fn(logits, target)
         loss.backward()
         opt.step()
+        last["logits"] = logits
         return loss
 
     def fence():
@@ -601,6 +649,12 @@ def main():
         elapsed = t.item()
     ms_per_step = elapsed / args.steps * 1e3
     wps = B * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:      # before anything below runs more steps
+        dump_outputs(args.dump_outputs, {
+            "logits": last["logits"], "loss": loss,
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in trainable]),
+            "params": torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]),
+            "buffers": torch.cat([b.reshape(-1).float() for b in model.buffers()])})
     par_info = None
     if world > 1:       # one more step with an event pair around every slice's all-reduce: makes an N-GPU line self-explaining
         sync = getattr(model, "_grad_sync", None)

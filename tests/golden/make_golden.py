@@ -178,6 +178,7 @@ def main():
     with torch.no_grad():
         d["logits_eval"] = npy(m(x))
     out["full_cfg1"] = d
+    out["full_cfg1_x"] = dict(x=d.pop("x"))      # the input alone: every fixture file stays under 1 MiB
 
     # state_dict contract (names + shapes) of the reference class built at the basic config
     sd = ref.MultiDimStacker(**orc.BASIC_CONFIG_KWARGS).state_dict()

@@ -71,7 +71,7 @@ def test_fp32_train_step_vs_oracle_128():
 
 def test_fp32_matches_reference_golden_config1(golden):
     """BASELINE configs[0] vectors produced by the reference's own MultiDimStacker code."""
-    d = golden("full_cfg1")
+    d = {**golden("full_cfg1"), **golden("full_cfg1_x")}      # (the input is a fixture of its own: files < 1 MiB)
     kw = dict(orc.BASIC_CONFIG_KWARGS, drop_rate=0.0, drop_path_rate=0.0)
     prod = mds.MultiDimStacker(**kw)
     fill_deterministic(prod, 14, scale=0.02)

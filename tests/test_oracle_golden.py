@@ -92,7 +92,7 @@ def test_tail_chain(golden):
 
 def test_full_model_config1(golden):
     """BASELINE.json configs[0]: 15-frame 128x128 stack, batch 1, CPU."""
-    d = golden("full_cfg1")
+    d = {**golden("full_cfg1"), **golden("full_cfg1_x")}      # (the input is a fixture of its own: files < 1 MiB)
     m = _mk({}, 14, scale=0.02).train()
     logits = m(T(d["x"]))
     loss = orc.sigmoid_focal_loss(logits, T(d["target"]), alpha=-1.0, gamma=1.2)

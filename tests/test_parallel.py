@@ -162,7 +162,7 @@ def test_bench_line_of_two_ranks_runs_end_to_end(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "1",
-                        "--no-cpu-baseline", "--no-pmc", "--no-other-configs"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-pmc", "--no-other-configs"], env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     d = json.loads(lines[0])

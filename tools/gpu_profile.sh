@@ -1,20 +1,20 @@
 #!/bin/bash
-# Developer tool (runs ON the GPU box through gpurun): bench line + rocprofv3 kernel stats + PMC passes.
-#   gpurun --timeout 1500 -- 'bash tools/gpu_profile.sh r02a [extra bench args]'
-# Writes gpurun_out/<tag>_*; the summaries worth judging are copied to profiles/ by hand afterwards.
+# Developer tool (runs on the MI355X box): full bench line + rocprofv3 kernel stats + PMC passes.
+#   bash tools/gpu_profile.sh r02a [extra bench args]
+# Writes $MDS_PROFILE_OUT/<tag>_* (default profile_out/); the summaries worth judging are copied to profiles/ by hand afterwards.
 # PMC passes are separate rocprofv3 runs with --pmc only (never combined with trace domains).
 set -u
 TAG=${1:-run}; shift || true
 EXTRA="$*"
 ROOT=$(pwd)
-OUT=$ROOT/gpurun_out
+OUT=$(realpath -m ${MDS_PROFILE_OUT:-profile_out})
 mkdir -p $OUT
 export TMPDIR=/tmp
 PY=python
 BENCH="$ROOT/bench.py"
 SHORT="--steps 3 --warmup 2 --profile-steps 0 --no-cpu-baseline --no-pmc --no-other-configs $EXTRA"   # (the child configs under --pmc took 40 GPU-minutes once)
 
-echo "== bench" ; $PY $BENCH $EXTRA > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err ; tail -c 600 $OUT/${TAG}_bench.err
+echo "== bench" ; $PY $BENCH --full $EXTRA > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err ; tail -c 600 $OUT/${TAG}_bench.err
 
 if [ "${SKIP_TRACE:-0}" != "1" ]; then
   echo "== kernel trace"
