@@ -41,7 +41,6 @@ struct C3Args {
   int tapw[9];         // weight slot of tap (dy, dx) at [3 * (dy + 1) + (dx + 1)]
   int nbands, nseg, rps, items;
   int RA, NR;
-  int dbg;             // MDS_KNOB_C3_DBG bits
   // post statistics (mds_poststat_t; PLAIN, or MASK with one value per image): sum g, sum g * xhat of the BatchNorm below
   const bf16_t* py; const float* pbn; const float* pmask; double* pstats;
   const float* pro_scale; const float* pro_shift;      // NTW > 0: the input is read through BatchNorm + SiLU (mds_pro_t BN_SILU)
@@ -1876,81 +1875,6 @@ __global__ __launch_bounds__(64 * (4 + NPW + NTW)) void c3wp_kernel(C3WArgs g) {
   for (int e = tid; e < 16 * SLAB; e += 256) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; atomicAdd(g.dw + ee, fl[ee]); }
 }
 
-template <int NPW, int NTW>
-static int c3wp_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_stream_t stream) {
-  constexpr int PPX = 4, PPY = 2, WB = 64;
-  constexpr int XS = (WB + 2) * PPX, XSP = (XS + 63) / 64 * 64, RS = XSP + WB * PPY, PIECES = RS / 64, ROWB = RS * 16;
-  C3WArgs g;
-  g.x = (const bf16_t*)a->x; g.dy = (const bf16_t*)a->dyt; g.dw = a->dw;
-  g.N = a->N; g.H = a->IH; g.W = a->IW; g.Ctot = a->Cout; g.wtaps = a->wtaps;
-  g.pro_scale = a->pro.scale; g.pro_shift = a->pro.shift;
-  for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
-  const int pcw = (PIECES + NPW - 1) / NPW;
-  int RA = (100 * 1024 + ROWB - 1) / ROWB;      // rows in flight: the ring is the whole LDS (a batch dips it by three rows)
-  while (RA > 3 && pcw * (RA - 1) > 40) --RA;
-  int NR = RA + 2 * C3WP_BATCH + 2;      // the batch being consumed + the one being transformed + the entry above / below
-  const size_t lds_cap = 158 * 1024;
-  while ((size_t)NR * ROWB > lds_cap && RA > 3) { --RA; NR = RA + 2 * C3WP_BATCH + 2; }
-  if ((size_t)NR * ROWB > lds_cap || pcw * (RA - 1) > 40) return 0;
-  g.RA = RA; g.NR = NR;
-  int CUS = 256;
-  if (mds_knob(MDS_KNOB_CONV_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_CONV_BLOCKS);
-  g.nbands = cdiv(a->IW, WB);
-  long best = -1;
-  for (int ns = 1; ns <= 64 && ns <= a->IH; ++ns) {
-    const int rps = cdiv(a->IH, ns), nsr = cdiv(a->IH, rps);
-    const long items = (long)a->N * g.nbands * nsr;
-    const long per = (items + CUS - 1) / CUS;
-    const long cost = per * (rps + 2 + 2);
-    if (best < 0 || cost < best) { best = cost; g.nseg = nsr; g.rps = rps; g.items = (int)items; }
-  }
-  const int grid = g.items < CUS ? g.items : CUS;
-  size_t smem = (size_t)NR * ROWB;
-  if (smem < (size_t)16 * 32 * 9 * 4) smem = (size_t)16 * 32 * 9 * 4;
-  MDS_LAUNCH((c3wp_kernel<NPW, NTW>), dim3(grid), dim3(64 * (4 + NPW + NTW)), smem, stream, g);
-  return 1;
-}
-
-template <int CIN, int COW, int NCW, int NPW>
-static int c3w_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_stream_t stream) {
-  constexpr int COP = 16 * COW * NCW, PPX = CIN / 8, PPY = COP / 8, WB = 32;
-  constexpr int XS = (WB + 2) * PPX, XSP = (XS + 63) / 64 * 64, RS = XSP + WB * PPY, PIECES = RS / 64, ROWB = RS * 16;
-  if (a->Cout % COP) return 0;
-  C3WArgs g;
-  g.x = (const bf16_t*)a->x; g.dy = (const bf16_t*)a->dyt; g.dw = a->dw;
-  g.N = a->N; g.H = a->IH; g.W = a->IW; g.Ctot = a->Cout; g.wtaps = a->wtaps; g.pro_scale = nullptr; g.pro_shift = nullptr;
-  for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
-  const int passes = a->Cout / COP;
-  const int pcw = (PIECES + NPW - 1) / NPW;
-  int RA = (80 * 1024 + ROWB - 1) / ROWB;
-  if (RA < 3) RA = 3;
-  while (RA > 3 && pcw * (RA - 1) > 40) --RA;
-  if (pcw * (RA - 1) > 40) return 0;
-  int NR = RA + 6;                                     // the consumers read back to entry k0 - 2 of the batch (+ one of slack)
-  const size_t lds_cap = 158 * 1024;
-  while ((size_t)NR * ROWB > lds_cap && RA > 3) { --RA; NR = RA + 6; }
-  if ((size_t)NR * ROWB > lds_cap) return 0;
-  g.RA = RA; g.NR = NR;
-  int CUS = 256 / passes;
-  if (mds_knob(MDS_KNOB_CONV_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_CONV_BLOCKS);
-  g.nbands = cdiv(a->IW, WB);
-  long best = -1;
-  for (int ns = 1; ns <= 64 && ns <= a->IH; ++ns) {
-    const int rps = cdiv(a->IH, ns), nsr = cdiv(a->IH, rps);
-    const long items = (long)a->N * g.nbands * nsr;
-    const long per = (items + CUS - 1) / CUS;
-    const long cost = per * (rps + 2 + 2);
-    if (best < 0 || cost < best) { best = cost; g.nseg = nsr; g.rps = rps; g.items = (int)items; }
-  }
-  const int grid = g.items < CUS ? g.items : CUS;
-  size_t smem = (size_t)NR * ROWB;
-  const size_t flush = (size_t)4 * 16 * CIN * 9 * 4;
-  if (smem < flush) smem = flush;
-  dim3 block(64 * (NCW + NPW));
-  MDS_LAUNCH((c3w_kernel<CIN, COW, NCW, NPW>), dim3(grid, passes), block, smem, stream, g);
-  return 1;
-}
-
 // The same for a STRIDE-2 layer (TF-SAME, even extents: blocks.2.0, 32 -> 128): dw[co][ci][ky][kx] += sum dy[r][x][co] in[2 r + ky][2 x + kx][ci].
 // A ring entry is dy row r of a 32-column band with ITS two input rows 2 r and 2 r + 1 (65 pixels each): the even row meets dy row r
 // (ky = 0) and dy row r - 1 (ky = 2, from the entry before - no look-ahead), the odd row meets dy row r (ky = 1); an item ends with one
@@ -2141,357 +2065,282 @@ __global__ __launch_bounds__(64 * (8 + NPW)) void c3w2_kernel(C3WArgs g) {      
   }
 }
 
-static int c3w2_try(const mds_conv_wgrad_args* a, mds_stream_t stream) {
-  constexpr int NPW = 3, WB = 32, XSP = ((2 * WB + 1) * 4 + 63) / 64 * 64, RS = 2 * XSP + WB * 16, PIECES = RS / 64, ROWB = RS * 16;
-  if (a->Cin != 32 || a->Cout != 128 || a->pro.mode != MDS_PRO_NONE || (mds_knob(MDS_KNOB_C3_DBG) & 512)) return 0;
-  if (a->IH % 2 || a->IW % 2 || a->OH != a->IH / 2 || a->OW != a->IW / 2) return 0;
-  if ((long)a->IH * a->IW * a->Cin >= (1L << 30) || (long)a->OH * a->OW * a->Cout >= (1L << 30)) return 0;
-  int tapw[9];
-  for (int t = 0; t < 9; ++t) tapw[t] = -1;
-  for (int t = 0; t < 9; ++t) {
-    if (a->dy[t] < 0 || a->dy[t] > 2 || a->dx[t] < 0 || a->dx[t] > 2) return 0;
-    tapw[3 * a->dy[t] + a->dx[t]] = a->wi[t];
-  }
-  for (int t = 0; t < 9; ++t) if (tapw[t] < 0 || tapw[t] >= 9) return 0;
-  if ((long)a->N * a->OH * a->OW < 16384 && mds_knob(MDS_KNOB_C3) != 2) return 0;
-  C3WArgs g;
-  g.x = (const bf16_t*)a->x; g.dy = (const bf16_t*)a->dyt; g.dw = a->dw;
-  g.N = a->N; g.H = a->IH; g.W = a->IW; g.Ctot = a->Cout; g.wtaps = a->wtaps; g.pro_scale = nullptr; g.pro_shift = nullptr;
-  for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
-  const int pcw = (PIECES + NPW - 1) / NPW;
-  int RA = 5;
-  while (RA > 2 && ((size_t)(RA + 3) * ROWB > 158 * 1024 || pcw * (RA - 1) > 40)) --RA;
-  if ((size_t)(RA + 3) * ROWB > 158 * 1024) return 0;
-  g.RA = RA; g.NR = RA + 3;
-  int CUS = 256;
-  if (mds_knob(MDS_KNOB_CONV_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_CONV_BLOCKS);
-  g.nbands = cdiv(a->OW, WB);
-  long best = -1;
-  for (int ns = 1; ns <= 64 && ns <= a->OH; ++ns) {
-    const int rps = cdiv(a->OH, ns), nsr = cdiv(a->OH, rps);
-    const long items = (long)a->N * g.nbands * nsr;
-    const long per = (items + CUS - 1) / CUS;
-    const long cost = per * (rps + 1 + 2);
-    if (best < 0 || cost < best) { best = cost; g.nseg = nsr; g.rps = rps; g.items = (int)items; }
-  }
-  const int grid = g.items < CUS ? g.items : CUS;
-  MDS_LAUNCH((c3w2_kernel<NPW>), dim3(grid, 1), dim3(64 * (8 + NPW)), (size_t)g.NR * ROWB, stream, g);
-  return 1;
-}
-
-// mds_conv_wgrad's large prologue-free stride-1 bf16 launches; 1 = launched, 0 = not one of these (k_conv.hip's kernel)
-int c3w_try(const mds_conv_wgrad_args* a, mds_stream_t stream) {
-  if (mds_knob(MDS_KNOB_C3) == 1 || (mds_knob(MDS_KNOB_C3_DBG) & 128)) return 0;
-  if (a->dtype == MDS_BF16 && a->is == 2 && a->ntaps == 9 && a->wtaps == 9) return c3w2_try(a, stream);
-  const bool pro = a->pro.mode == MDS_PRO_BN_SILU;
-  if (a->dtype != MDS_BF16 || a->is != 1 || a->ntaps != 9 || a->wtaps != 9 || (a->pro.mode != MDS_PRO_NONE && !pro)) return 0;
-  if (pro && !(a->Cin == 32 && a->Cout == 16 && a->pro.scale && a->pro.shift && !(mds_knob(MDS_KNOB_C3_DBG) & 256))) return 0;
-  if (a->OH != a->IH || a->OW != a->IW) return 0;
-  if ((long)a->IH * a->IW * a->Cout >= (1L << 30)) return 0;
-  int tapw[9];
-  for (int t = 0; t < 9; ++t) tapw[t] = -1;
-  for (int t = 0; t < 9; ++t) {
-    if (a->dy[t] < -1 || a->dy[t] > 1 || a->dx[t] < -1 || a->dx[t] > 1) return 0;
-    tapw[3 * (a->dy[t] + 1) + a->dx[t] + 1] = a->wi[t];
-  }
-  for (int t = 0; t < 9; ++t) if (tapw[t] < 0 || tapw[t] >= 9) return 0;
-  if ((long)a->N * a->IH * a->IW < 16384 && mds_knob(MDS_KNOB_C3) != 2) return 0;
-  if (pro) return c3wp_launch<3, 8>(a, tapw, stream);      // blocks.0.0: behind the stem's BatchNorm + SiLU
-  if (a->Cin == 32 && a->Cout == 128) return c3w_launch<32, 1, 8, 3>(a, tapw, stream);      // blocks.1.1: eight consumer waves of one 16-channel fragment each
-  if (a->Cin == 48 && a->Cout == 192) return c3w_launch<48, 1, 6, 2>(a, tapw, stream);      // blocks.2.1: two passes of 96 channels, six consumer waves
-  return 0;
-}
-
 // host side ------------------------------------------------------------------------------------------------------------
-template <int CIN, int NF, int NSPL, int SPW, int NPW, int NSW, bool ONE = false, int NTW = 0>
-static int c3_launch(const mds_conv_fwd_args* a, const int (&tapw)[9], mds_stream_t stream) {
-  typedef C3Cfg<CIN, NF, NSPL, SPW, true> CFR;
-  typedef C3Cfg<CIN, NF, NSPL, SPW, false> CFN;
-  typedef C3Cfg<CIN, NF, NSPL, SPW, true, true> CFP;
-  typedef C3Cfg<CIN, NF, NSPL, SPW, false, true> CFQ;
-  const bool res = a->residual != nullptr, stats = a->stats != nullptr, post = a->post.mode != MDS_POST_NONE;
-  if (post && stats) return 0;
-  const int WB = CFN::WB, rowb = post ? (res ? CFP::ROWB : CFQ::ROWB) : (res ? CFR::ROWB : CFN::ROWB);
-  const int pieces = post ? (res ? CFP::PIECES : CFQ::PIECES) : (res ? CFR::PIECES : CFN::PIECES);
-  C3Args g;
-  g.x = (const bf16_t*)a->x; g.w = (const bf16_t*)a->w; g.y = (bf16_t*)a->y; g.res = (const bf16_t*)a->residual; g.stats = a->stats;
-  g.N = a->N; g.H = a->IH; g.W = a->IW; g.OH = a->OH; g.OW = a->OW; g.wtaps = a->wtaps; g.Ctot = a->Cout;
-  const int passes = a->Cout / CFN::COUT;
-  for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
-  // rows in flight: ~40 KB per CU ahead of the consumers (HBM latency x a CU's share of the bandwidth), at least 3 rows;
-  // the producers' vmcnt (6 bits) carries pcw * (RA - 1) pieces
-  const int pcw = (pieces + NPW - 1) / NPW;
-  int RA = (64 * 1024 + rowb - 1) / rowb;
-  if (RA < 3) RA = 3;
-  while (RA > 3 && pcw * (RA - 1) > 40) --RA;
-  if (pcw * (RA - 1) > 40) return 0;
-  const int keep = (post ? 6 : 3) + (NTW ? 3 : 0);      // ring rows beyond the RA in flight: the batch being read (+ with post statistics the one before: its y rows serve the store waves)
-  int NR = RA + keep;
-  const size_t lds_cap = 155 * 1024 - 6 * (size_t)WB * CFN::COUT * 2 - 2 * CIN * 4;     // the staged output rows share the LDS
-  while ((size_t)NR * rowb > lds_cap && RA > 3) { --RA; NR = RA + keep; }
-  if ((size_t)NR * rowb > lds_cap) return 0;
-  g.RA = RA; g.NR = NR; g.dbg = mds_knob(MDS_KNOB_C3_DBG); g.trace = (void*)a->epi.scale;
-  g.py = (const bf16_t*)a->post.y; g.pbn = a->post.bn; g.pmask = a->post.mode == MDS_POST_MASK ? a->post.mask : nullptr; g.pstats = a->post.stats; g.pmode = a->post.mode;
-  // items: bands x row segments, the segment count that minimises the longest block's rows (+2 halo rows, + a fill per item)
-  int CUS = 256 / passes;
-  if (!stats && mds_knob(MDS_KNOB_C3_BWD_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_C3_BWD_BLOCKS) / passes;
-  if (mds_knob(MDS_KNOB_CONV_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_CONV_BLOCKS);      // tests: few blocks, many items each
-  g.nbands = cdiv(a->IW, WB);
+// c3_fwd_route / c3w_route choose the kernel, the instance and the tap map without side effects; a launcher cannot decline: its ring
+// geometry is a compile-time fact of the instance and its residual / post form, static_asserted to fit (C3Ring).
+// tapw[3 ky + kx] = the weight slot of tap (ky, kx): true when the taps hit each of the nine once, with slots below `bound`.  The taps
+// are nine of form `form` (gn = nullptr) or ngroups groups of gn[i] in forms gpy[i] (rows) and gpx[i] (columns).  Forms: C3_S1
+// centred stride-1 offsets -1..1, C3_S2 stride-2 offsets 0..2, or 0 / 1: the transposed kernel at that output parity (pads 0: output
+// 2a + p reads input a + d with (p, d) in {(0, 0): k 0, (0, -1): k 2, (1, 0): k 1})
+enum { C3_S1 = 2, C3_S2 = 3 };
+static bool c3_tapmap(int (&tapw)[9], const int* dy, const int* dx, const int* wi, int bound, int form, int ngroups = 1,
+                      const int* gn = nullptr, const int* gpy = nullptr, const int* gpx = nullptr) {
+  auto tap_k = [](int f, int d) { const int k = f == C3_S1 ? d + 1 : f == C3_S2 ? d : f == 0 ? (d == 0 ? 0 : 2 * -d) : f == 1 && d == 0 ? 1 : -1; return k >= 0 && k <= 2 ? k : -1; };
+  for (int u = 0; u < 9; ++u) tapw[u] = -1;
+  for (int gi = 0, t = 0; gi < ngroups; ++gi)
+    for (int u = 0; u < (gn ? gn[gi] : 9); ++u, ++t) {
+      const int ky = t < 9 ? tap_k(gn ? gpy[gi] : form, dy[t]) : -1, kx = t < 9 ? tap_k(gn ? gpx[gi] : form, dx[t]) : -1;
+      if (ky < 0 || kx < 0 || tapw[3 * ky + kx] >= 0) return false;
+      tapw[3 * ky + kx] = wi[t];
+    }
+  for (int u = 0; u < 9; ++u) if (tapw[u] < 0 || tapw[u] >= bound) return false;
+  return true;
+}
+
+// ring of a row-streaming launch: RA rows in flight - BYTES of rows ahead but at least LO, then fewer (not below LO) while the producers'
+// vmcnt (6 bits) would carry more than 40 pieces (PCW per row) or the RA + KEEP ring rows would pass the LDS cap - and NR ring rows
+template <int ROWB, int PIECES, int NPW, int BYTES, int LO, int KEEP, long CAP> struct C3Ring {
+  static constexpr int PCW = (PIECES + NPW - 1) / NPW;
+  static constexpr int ra() {
+    int RA = (BYTES + ROWB - 1) / ROWB > LO ? (BYTES + ROWB - 1) / ROWB : LO;
+    while (RA > LO && PCW * (RA - 1) > 40) --RA;
+    while (RA > LO && (long)(RA + KEEP) * ROWB > CAP) --RA;
+    return RA;
+  }
+  static constexpr int RA = ra(), NR = RA + KEEP;
+  static_assert(PCW * (RA - 1) <= 40, "the ring passes the producers' vmcnt budget");
+  static_assert((long)NR * ROWB <= CAP, "the ring passes the LDS cap");
+};
+// blocks of a persistent launch: one per CU, shared by the `passes` channel slices (grid.y); MDS_KNOB_C3_BWD_BLOCKS where `bwd`
+// (data gradients beside the weight-gradient stream), MDS_KNOB_CONV_BLOCKS anywhere (tests: few blocks, many items each)
+static int c3_blocks(int passes, bool bwd) {
+  const int cb = mds_knob(MDS_KNOB_CONV_BLOCKS), bb = bwd ? mds_knob(MDS_KNOB_C3_BWD_BLOCKS) : 0;
+  return cb > 0 ? cb : (bb > 0 ? bb : mds_cu_count()) / passes;
+}
+// work items = images x nbands bands x segments of `rows` rows: the segment count that minimises the longest block's cost,
+// per * (k * rows per segment + c) (+ halo rows and a fill per item); the first of equal costs wins.  -> grid.x
+template <class G> static int c3_split(G& g, int rows, int nbands, int blocks, int k, int c) {
+  g.nbands = nbands;
   long best = -1;
-  for (int ns = 1; ns <= 64 && ns <= a->IH; ++ns) {
-    const int rps = cdiv(a->IH, ns), nsr = cdiv(a->IH, rps);
-    const long items = (long)a->N * g.nbands * nsr;
-    const long per = (items + CUS - 1) / CUS;
-    const long cost = per * (rps + 2 + 2);
+  for (int ns = 1; ns <= 64 && ns <= rows; ++ns) {
+    const int rps = cdiv(rows, ns), nsr = cdiv(rows, rps);
+    const long items = (long)g.N * nbands * nsr, cost = (items + blocks - 1) / blocks * (k * rps + c);
     if (best < 0 || cost < best) { best = cost; g.nseg = nsr; g.rps = rps; g.items = (int)items; }
   }
-  const int grid = g.items < CUS ? g.items : CUS;
-  size_t smem = (size_t)NR * rowb + 6 * (size_t)WB * CFN::COUT * 2;
+  return g.items < blocks ? g.items : blocks;
+}
+static C3Args c3_args(const mds_conv_fwd_args* a, const int (&tapw)[9], int RA, int NR) {
+  C3Args g = {};
+  g.x = (const bf16_t*)a->x; g.w = (const bf16_t*)a->w; g.y = (bf16_t*)a->y; g.res = (const bf16_t*)a->residual; g.stats = a->stats;
+  g.N = a->N; g.H = a->IH; g.W = a->IW; g.OH = a->OH; g.OW = a->OW; g.wtaps = a->wtaps; g.Ctot = a->Cout; g.RA = RA; g.NR = NR;
+  g.pro_scale = a->pro.scale; g.pro_shift = a->pro.shift; g.trace = (void*)a->epi.scale; for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
+  g.py = (const bf16_t*)a->post.y; g.pbn = a->post.bn; g.pmask = a->post.mode == MDS_POST_MASK ? a->post.mask : nullptr; g.pstats = a->post.stats; g.pmode = a->post.mode;
+  return g;
+}
+static C3WArgs c3w_args(const mds_conv_wgrad_args* a, const int (&tapw)[9], int RA, int NR) {
+  C3WArgs g = {};
+  g.x = (const bf16_t*)a->x; g.dy = (const bf16_t*)a->dyt; g.dw = a->dw; g.pro_scale = a->pro.scale; g.pro_shift = a->pro.shift;
+  g.N = a->N; g.H = a->IH; g.W = a->IW; g.Ctot = a->Cout; g.wtaps = a->wtaps; g.RA = RA; g.NR = NR; for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
+  return g;
+}
+
+template <class A> using C3Launch = void (*)(const A*, const int (&)[9], mds_stream_t);
+template <class A> struct C3Route { C3Launch<A> launch; int tapw[9]; };      // launch nullptr: not a shape of these kernels
+template <class A> static int c3_go(const C3Route<A>& r, const A* a, mds_stream_t s) { if (r.launch) r.launch(a, r.tapw, s); return r.launch != nullptr; }
+template <int NPW, int NTW>
+static void c3wp_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_stream_t stream) {
+  constexpr int PPX = 4, PPY = 2, WB = 64, XS = (WB + 2) * PPX, XSP = (XS + 63) / 64 * 64, RS = XSP + WB * PPY, PIECES = RS / 64, ROWB = RS * 16;
+  // the ring is the whole LDS (a batch dips it by three rows): the batch being consumed + the one being transformed + the entry above / below
+  typedef C3Ring<ROWB, PIECES, NPW, 100 * 1024, 3, 2 * C3WP_BATCH + 2, 158 * 1024> R;
+  C3WArgs g = c3w_args(a, tapw, R::RA, R::NR);
+  const int grid = c3_split(g, a->IH, cdiv(a->IW, WB), c3_blocks(1, false), 1, 4);
+  const size_t smem = (size_t)R::NR * ROWB > (size_t)16 * 32 * 9 * 4 ? (size_t)R::NR * ROWB : (size_t)16 * 32 * 9 * 4;
+  MDS_LAUNCH((c3wp_kernel<NPW, NTW>), dim3(grid), dim3(64 * (4 + NPW + NTW)), smem, stream, g);
+}
+template <int CIN, int COW, int NCW, int NPW>
+static void c3w_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_stream_t stream) {
+  constexpr int COP = 16 * COW * NCW, PPX = CIN / 8, PPY = COP / 8, WB = 32, XS = (WB + 2) * PPX, XSP = (XS + 63) / 64 * 64, RS = XSP + WB * PPY, PIECES = RS / 64, ROWB = RS * 16;
+  typedef C3Ring<ROWB, PIECES, NPW, 80 * 1024, 3, 6, 158 * 1024> R;      // the consumers read back to entry k0 - 2 of the batch (+ one of slack)
+  C3WArgs g = c3w_args(a, tapw, R::RA, R::NR);
+  const int passes = a->Cout / COP, grid = c3_split(g, a->IH, cdiv(a->IW, WB), c3_blocks(passes, false), 1, 4);
+  const size_t flush = (size_t)4 * 16 * CIN * 9 * 4, smem = (size_t)R::NR * ROWB > flush ? (size_t)R::NR * ROWB : flush;
+  MDS_LAUNCH((c3w_kernel<CIN, COW, NCW, NPW>), dim3(grid, passes), dim3(64 * (NCW + NPW)), smem, stream, g);
+}
+template <int NPW>
+static void c3w2_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_stream_t stream) {
+  constexpr int WB = 32, XSP = ((2 * WB + 1) * 4 + 63) / 64 * 64, RS = 2 * XSP + WB * 16, PIECES = RS / 64, ROWB = RS * 16;
+  typedef C3Ring<ROWB, PIECES, NPW, 5 * ROWB, 2, 3, 158 * 1024> R;      // five entries in flight
+  C3WArgs g = c3w_args(a, tapw, R::RA, R::NR);
+  const int grid = c3_split(g, a->OH, cdiv(a->OW, WB), c3_blocks(1, false), 1, 3);
+  MDS_LAUNCH((c3w2_kernel<NPW>), dim3(grid, 1), dim3(64 * (8 + NPW)), (size_t)R::NR * ROWB, stream, g);
+}
+// mds_conv_wgrad's large bf16 launches: blocks.1.1 / 2.1, 2.0 (stride 2, TF-SAME pads 0 / 1, even extents), 0.0 (behind the stem's BN + SiLU)
+static C3Route<mds_conv_wgrad_args> c3w_route(const mds_conv_wgrad_args* a) {
+  C3Route<mds_conv_wgrad_args> r = {};
+  const int knob = mds_knob(MDS_KNOB_C3); const bool pro = a->pro.mode == MDS_PRO_BN_SILU;
+  if (knob == 1 || a->dtype != MDS_BF16 || a->ntaps != 9 || a->wtaps != 9) return r;
+  if (a->is == 2) {
+    if (a->Cin != 32 || a->Cout != 128 || a->pro.mode != MDS_PRO_NONE) return r;
+    if (a->IH % 2 || a->IW % 2 || a->OH != a->IH / 2 || a->OW != a->IW / 2) return r;
+    if ((long)a->IH * a->IW * a->Cin >= (1L << 30) || (long)a->OH * a->OW * a->Cout >= (1L << 30)) return r;
+    if (c3_tapmap(r.tapw, a->dy, a->dx, a->wi, 9, C3_S2) && ((long)a->N * a->OH * a->OW >= 16384 || knob == 2)) r.launch = c3w2_launch<3>;
+    return r;
+  }
+  if (a->is != 1 || (a->pro.mode != MDS_PRO_NONE && !pro) || a->OH != a->IH || a->OW != a->IW) return r;
+  if (pro && !(a->Cin == 32 && a->Cout == 16 && a->pro.scale && a->pro.shift)) return r;
+  if ((long)a->IH * a->IW * a->Cout >= (1L << 30)) return r;
+  if (!c3_tapmap(r.tapw, a->dy, a->dx, a->wi, 9, C3_S1) || ((long)a->N * a->IH * a->IW < 16384 && knob != 2)) return r;
+  if (pro) r.launch = c3wp_launch<3, 8>;
+  else if (a->Cin == 32 && a->Cout == 128) r.launch = c3w_launch<32, 1, 8, 3>;      // blocks.1.1: eight consumer waves of one 16-channel fragment each
+  else if (a->Cin == 48 && a->Cout == 192) r.launch = c3w_launch<48, 1, 6, 2>;      // blocks.2.1: two passes of 96 channels, six consumer waves
+  return r;
+}
+
+int c3w_try(const mds_conv_wgrad_args* a, mds_stream_t stream) { return c3_go(c3w_route(a), a, stream); }      // 1 = launched, 0 = k_conv.hip's kernel
+
+template <int CIN, int NF, int NSPL, int SPW, int NPW, int NSW, bool ONE, int NTW, bool RES, bool POST>
+static void c3_launch(const mds_conv_fwd_args* a, const int (&tapw)[9], mds_stream_t stream) {
+  typedef C3Cfg<CIN, NF, NSPL, SPW, RES, POST> CF;
+  static_assert(!ONE || CF::WB == 32, "c3_pw_try's rows are whole bands");
+  // rows in flight: ~40 KB per CU ahead of the consumers (HBM latency x a CU's share of the bandwidth); the ring also keeps the batch being
+  // read (+ with post statistics the one before: its y rows serve the store waves; + the transform waves' batch) beside the staged output rows
+  constexpr int STAGE = 6 * CF::WB * CF::COUT * 2;
+  typedef C3Ring<CF::ROWB, CF::PIECES, NPW, 64 * 1024, 3, (POST ? 6 : 3) + (NTW ? 3 : 0), 155 * 1024 - STAGE - 2 * CIN * 4> R;
+  C3Args g = c3_args(a, tapw, R::RA, R::NR);
+  const bool stats = a->stats != nullptr, masked = a->IW % CF::WB != 0;
+  const int passes = a->Cout / CF::COUT;
+  const dim3 grid(c3_split(g, a->IH, cdiv(a->IW, CF::WB), c3_blocks(passes, !stats), 1, 4), passes), block(256 + 64 * (NPW + NSW + NTW));
+  size_t smem = (size_t)R::NR * CF::ROWB + STAGE;
 #ifdef C3_TRACE
   smem += 160 * 32 * 8;
 #endif
-  dim3 block(256 + 64 * (NPW + NSW + NTW));
-  const bool masked = a->IW % WB != 0;
-  g.pro_scale = a->pro.scale; g.pro_shift = a->pro.shift;
-  if (NTW) {
-    if (res || post || ONE) return 0;
-#define C3_GOT(S, M) MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, false, S, M, false, false, NTW>), dim3(grid, passes), block, smem, stream, g)
-    if (stats) { if (masked) C3_GOT(true, true); else C3_GOT(true, false); }
-    else { if (masked) C3_GOT(false, true); else C3_GOT(false, false); }
-#undef C3_GOT
-    return 1;
-  }
-#define C3_GO(R, S) do { if (masked) MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, R, S, true, false, ONE>), dim3(grid, passes), block, smem, stream, g); \
-                         else MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, R, S, false, false, ONE>), dim3(grid, passes), block, smem, stream, g); } while (0)
-  if (ONE) {
-    if (post || stats || masked) return 0;
-    if (res) MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, true, false, false, false, true>), dim3(grid, passes), block, smem, stream, g);
-    else MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, false, false, false, false, true>), dim3(grid, passes), block, smem, stream, g);
-  } else if (post) {
-#define C3_GOP(R, M) MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, R, false, M, true>), dim3(grid, passes), block, smem, stream, g)
-    if (res) { if (masked) C3_GOP(true, true); else C3_GOP(true, false); }
-    else { if (masked) C3_GOP(false, true); else C3_GOP(false, false); }
-#undef C3_GOP
-  } else if (res) { if (stats) return 0; C3_GO(true, false); }      // (a residual operand and statistics never meet in the network)
-  else { if (stats) C3_GO(false, true); else C3_GO(false, false); }
+#define C3_GO(S, M) MDS_LAUNCH((c3_kernel<CIN, NF, NSPL, SPW, NPW, NSW, RES, S, M, POST, ONE, NTW>), grid, block, smem, stream, g)
+  if constexpr (ONE) C3_GO(false, false);
+  else if constexpr (RES || POST) { if (masked) C3_GO(false, true); else C3_GO(false, false); }      // (no statistics: c3_fwd_route)
+  else if (stats) { if (masked) C3_GO(true, true); else C3_GO(true, false); }
+  else { if (masked) C3_GO(false, true); else C3_GO(false, false); }
 #undef C3_GO
-  return 1;
 }
 
+// an instance's c3_kernel launcher for the residual / post flags; FORMS: the (residual, post) forms it is built for
+enum { C3_PLAIN = 1, C3_RES = 2, C3_POST = 4, C3_RESPOST = 8, C3_ALL = 15 };
+template <int FORMS, int CIN, int NF, int NSPL, int SPW, int NPW, int NSW, bool ONE = false, int NTW = 0>
+static C3Launch<mds_conv_fwd_args> c3_pick(bool res, bool post) {
+  const int form = res ? (post ? C3_RESPOST : C3_RES) : (post ? C3_POST : C3_PLAIN);
+  if constexpr ((FORMS & C3_PLAIN) != 0) { if (form == C3_PLAIN) return c3_launch<CIN, NF, NSPL, SPW, NPW, NSW, ONE, NTW, false, false>; }
+  if constexpr ((FORMS & C3_RES) != 0) { if (form == C3_RES) return c3_launch<CIN, NF, NSPL, SPW, NPW, NSW, ONE, NTW, true, false>; }
+  if constexpr ((FORMS & C3_POST) != 0) { if (form == C3_POST) return c3_launch<CIN, NF, NSPL, SPW, NPW, NSW, ONE, NTW, false, true>; }
+  if constexpr ((FORMS & C3_RESPOST) != 0) { if (form == C3_RESPOST) return c3_launch<CIN, NF, NSPL, SPW, NPW, NSW, ONE, NTW, true, true>; }
+  return nullptr;
+}
 
-template <int CIN, int NF, int NSPL, int NPW, int NSW>
-static int c3t_launch(const mds_conv_fwd_args* a, const int (&tapw)[9], mds_stream_t stream) {
-  constexpr int PP = CIN / 8, NSG = 4 / NSPL, WBI = 16 * NSG, COUT = 16 * NF * NSPL;
-  const bool post = a->post.mode != MDS_POST_NONE;
-  constexpr int RSX = (WBI + 1) * PP, RPYP = (RSX + 63) / 64 * 64;
-  const int RS = post ? RPYP + 2 * (2 * WBI) * (COUT / 8) : RSX, PIECES = (RS + 63) / 64, ROWB = RS * 16;
-  C3Args g;
-  g.x = (const bf16_t*)a->x; g.w = (const bf16_t*)a->w; g.y = (bf16_t*)a->y; g.res = nullptr; g.stats = nullptr;
-  g.N = a->N; g.H = a->IH; g.W = a->IW; g.OH = a->OH; g.OW = a->OW; g.wtaps = a->wtaps; g.Ctot = a->Cout;
-  for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
+template <int CIN, int NF, int NSPL, int NPW, int NSW, bool POST>
+static void c3t_launch(const mds_conv_fwd_args* a, const int (&tapw)[9], mds_stream_t stream) {
+  constexpr int PP = CIN / 8, NSG = 4 / NSPL, WBI = 16 * NSG, COUT = 16 * NF * NSPL, RSX = (WBI + 1) * PP, RPYP = (RSX + 63) / 64 * 64;
+  constexpr int RS = POST ? RPYP + 2 * (2 * WBI) * (COUT / 8) : RSX, PIECES = (RS + 63) / 64, ROWB = RS * 16, STAGE = 8 * (2 * WBI) * COUT * 2;
+  typedef C3Ring<ROWB, PIECES, NPW, 64 * 1024, 2, POST ? 4 : 2, 156 * 1024 - STAGE> R;
+  C3Args g = c3_args(a, tapw, R::RA, R::NR);
   const int passes = a->Cout / COUT;
-  const int pcw = (PIECES + NPW - 1) / NPW;
-  const size_t stage = 8 * (size_t)(2 * WBI) * COUT * 2;
-  int RA = (64 * 1024 + ROWB - 1) / ROWB;
-  if (RA < 2) RA = 2;
-  while (RA > 2 && pcw * (RA - 1) > 40) --RA;
-  if (pcw * (RA - 1) > 40) return 0;
-  const int keep = post ? 4 : 2;
-  int NR = RA + keep;
-  while ((size_t)NR * ROWB + stage > 156 * 1024 && RA > 2) { --RA; NR = RA + keep; }
-  if ((size_t)NR * ROWB + stage > 156 * 1024) return 0;
-  g.RA = RA; g.NR = NR; g.dbg = 0; g.trace = nullptr;
-  g.py = (const bf16_t*)a->post.y; g.pbn = a->post.bn; g.pmask = a->post.mode == MDS_POST_MASK ? a->post.mask : nullptr; g.pstats = a->post.stats; g.pmode = a->post.mode;
-  int CUS = 256 / passes;
-  if (mds_knob(MDS_KNOB_C3_BWD_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_C3_BWD_BLOCKS) / passes;
-  if (mds_knob(MDS_KNOB_CONV_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_CONV_BLOCKS);
-  g.nbands = cdiv(a->IW, WBI);
-  long best = -1;
-  for (int ns = 1; ns <= 64 && ns <= a->IH; ++ns) {
-    const int rps = cdiv(a->IH, ns), nsr = cdiv(a->IH, rps);
-    const long items = (long)a->N * g.nbands * nsr;
-    const long per = (items + CUS - 1) / CUS;
-    const long cost = per * (rps + 1 + 2);
-    if (best < 0 || cost < best) { best = cost; g.nseg = nsr; g.rps = rps; g.items = (int)items; }
-  }
-  const int grid = g.items < CUS ? g.items : CUS;
-  const size_t smem = (size_t)NR * ROWB + stage;
-  dim3 block(256 + 64 * (NPW + NSW));
-  const bool masked = 2 * a->IW != a->OW || a->IW % WBI != 0;
-#define C3T_GO(M, P) MDS_LAUNCH((c3t_kernel<CIN, NF, NSPL, NPW, NSW, M, P>), dim3(grid, passes), block, smem, stream, g)
-  if (post) { if (masked) C3T_GO(true, true); else C3T_GO(false, true); }
-  else { if (masked) C3T_GO(true, false); else C3T_GO(false, false); }
-#undef C3T_GO
-  return 1;
-}
-
-// post statistics as these kernels take them: PLAIN, SILU, or MASK with one factor per image
-static bool c3_post_ok(const mds_conv_fwd_args* a) {
-  if (a->post.mode == MDS_POST_NONE) return true;
-  if (a->post.mode != MDS_POST_PLAIN && a->post.mode != MDS_POST_MASK && a->post.mode != MDS_POST_SILU) return false;
-  if (!a->post.y || !a->post.bn || !a->post.stats) return false;
-  return a->post.mode != MDS_POST_MASK || (a->post.mask && a->post.rows_per_group == (long)a->OH * a->OW);
-}
-
-// the stride-2 data gradient as mds_conv_fwd receives it: four tap groups (one per output parity), is = 1, os = 2
-static int c3t_try(const mds_conv_fwd_args* a, mds_stream_t stream) {
-  if (a->dtype != MDS_BF16 || a->is != 1 || a->os != 2 || a->ngroups != 4 || a->ntaps != 9) return 0;
-  if (a->pro.mode != MDS_PRO_NONE || a->epi.mode != MDS_EPI_NONE || a->residual || a->stats) return 0;
-  if (!c3_post_ok(a)) return 0;
-  if (a->OH != 2 * a->IH && a->OH != 2 * a->IH - 1) return 0;
-  if (a->OW != 2 * a->IW && a->OW != 2 * a->IW - 1) return 0;
-  if ((long)a->OH * a->OW * (a->Cin > a->Cout ? a->Cin : a->Cout) >= (1L << 30)) return 0;
-  int tapw[9];
-  for (int t = 0; t < 9; ++t) tapw[t] = -1;
-  int t = 0;
-  for (int gi = 0; gi < 4; ++gi) {
-    const int py = a->g_oy0[gi], px = a->g_ox0[gi];
-    if (py < 0 || py > 1 || px < 0 || px > 1) return 0;
-    for (int u = 0; u < a->g_ntaps[gi]; ++u, ++t) {
-      // pads 0: output 2a + py reads input a + dy with (py, dy) in {(0, 0): ky 0, (0, -1): ky 2, (1, 0): ky 1}; the same in x
-      const int dy = a->dy[t], dx = a->dx[t];
-      const int ky = py == 1 ? (dy == 0 ? 1 : -1) : (dy == 0 ? 0 : (dy == -1 ? 2 : -1));
-      const int kx = px == 1 ? (dx == 0 ? 1 : -1) : (dx == 0 ? 0 : (dx == -1 ? 2 : -1));
-      if (ky < 0 || kx < 0 || tapw[3 * ky + kx] >= 0) return 0;
-      tapw[3 * ky + kx] = a->wi[t];
-    }
-  }
-  for (int u = 0; u < 9; ++u) if (tapw[u] < 0 || tapw[u] >= a->wtaps) return 0;
-  const long rows = (long)a->N * a->OH * a->OW;
-  if (rows < 16384 && mds_knob(MDS_KNOB_C3) != 2) return 0;
-  if (a->Cin == 128 && a->Cout == 32) return c3t_launch<128, 1, 2, 3, 1>(a, tapw, stream);
-  if (a->Cin == 64 && a->Cout == 16) return c3t_launch<64, 1, 1, 2, 2>(a, tapw, stream);
-  return 0;
+  const dim3 grid(c3_split(g, a->IH, cdiv(a->IW, WBI), c3_blocks(passes, true), 1, 3), passes), block(256 + 64 * (NPW + NSW));
+  const size_t smem = (size_t)R::NR * ROWB + STAGE;
+  if (2 * a->IW != a->OW || a->IW % WBI != 0) MDS_LAUNCH((c3t_kernel<CIN, NF, NSPL, NPW, NSW, true, POST>), grid, block, smem, stream, g);
+  else MDS_LAUNCH((c3t_kernel<CIN, NF, NSPL, NPW, NSW, false, POST>), grid, block, smem, stream, g);
 }
 
 template <int CIN, int NF, int NSPL, int SPW, int NPW, int NSW, int NTW>
-static int c3s_launch(const mds_conv_fwd_args* a, const int (&tapw)[9], mds_stream_t stream) {
+static void c3s_launch(const mds_conv_fwd_args* a, const int (&tapw)[9], mds_stream_t stream) {
   constexpr int PP = CIN / 8, NSG = 4 / NSPL, WB = 16 * NSG * SPW, COUT = 16 * NF * NSPL;
-  constexpr int RPX = (2 * WB + 1) * PP, PIECES = (RPX + 63) / 64, ROWB = RPX * 16, STGROW = WB * COUT * 2;
-  if (a->Cout % COUT) return 0;
-  C3Args g;
-  g.x = (const bf16_t*)a->x; g.w = (const bf16_t*)a->w; g.y = (bf16_t*)a->y; g.res = nullptr; g.stats = a->stats;
-  g.N = a->N; g.H = a->IH; g.W = a->IW; g.OH = a->OH; g.OW = a->OW; g.wtaps = a->wtaps; g.Ctot = a->Cout;
+  constexpr int RPX = (2 * WB + 1) * PP, PIECES = (RPX + 63) / 64, ROWB = RPX * 16, STAGE = 4 * WB * COUT * 2;
+  typedef C3Ring<ROWB, PIECES, NPW, 64 * 1024, 4, 4 + (NTW ? 4 : 0), 155 * 1024 - STAGE> R;      // keeps the batch being read (+ the one being transformed)
+  C3Args g = c3_args(a, tapw, R::RA, R::NR);
   const int passes = a->Cout / COUT;
-  for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
-  const int pcw = (PIECES + NPW - 1) / NPW;
-  int RA = (64 * 1024 + ROWB - 1) / ROWB;
-  if (RA < 4) RA = 4;
-  while (RA > 4 && pcw * (RA - 1) > 40) --RA;
-  if (pcw * (RA - 1) > 40) return 0;
-  const int keep = 4 + (NTW ? 4 : 0);       // ring rows beyond the RA in flight: the batch being read (+ the one being transformed)
-  int NR = RA + keep;
-  const size_t lds_cap = 155 * 1024 - 4 * (size_t)STGROW;
-  while ((size_t)NR * ROWB > lds_cap && RA > 4) { --RA; NR = RA + keep; }
-  if ((size_t)NR * ROWB > lds_cap) return 0;
-  g.RA = RA; g.NR = NR; g.dbg = 0; g.trace = nullptr;
-  g.py = nullptr; g.pbn = nullptr; g.pmask = nullptr; g.pstats = nullptr; g.pmode = 0;
-  g.pro_scale = a->pro.scale; g.pro_shift = a->pro.shift;
-  int CUS = 256 / passes;
-  if (mds_knob(MDS_KNOB_CONV_BLOCKS) > 0) CUS = mds_knob(MDS_KNOB_CONV_BLOCKS);
-  g.nbands = cdiv(a->OW, WB);
-  long best = -1;
-  for (int ns = 1; ns <= 64 && ns <= a->OH; ++ns) {
-    const int rps = cdiv(a->OH, ns), nsr = cdiv(a->OH, rps);
-    const long items = (long)a->N * g.nbands * nsr;
-    const long per = (items + CUS - 1) / CUS;
-    const long cost = per * (2 * rps + 1 + 4);
-    if (best < 0 || cost < best) { best = cost; g.nseg = nsr; g.rps = rps; g.items = (int)items; }
-  }
-  const int grid = g.items < CUS ? g.items : CUS;
-  const size_t smem = (size_t)NR * ROWB + 4 * (size_t)STGROW;
-  dim3 block(256 + 64 * (NPW + NSW + NTW));
+  const dim3 grid(c3_split(g, a->OH, cdiv(a->OW, WB), c3_blocks(passes, false), 2, 5), passes), block(256 + 64 * (NPW + NSW + NTW));
+  const size_t smem = (size_t)R::NR * ROWB + STAGE;
   const bool masked = a->OW % WB != 0, stats = a->stats != nullptr;
-#define C3S_GO(S, M) MDS_LAUNCH((c3s_kernel<CIN, NF, NSPL, SPW, NPW, NSW, S, M, NTW>), dim3(grid, passes), block, smem, stream, g)
-  if (masked) {
-    // (the transform-wave form runs three waves per SIMD - 168 VGPRs - and its column-masked statistics variant spills 34 of them: the
-    //  network's widths are whole bands, ragged widths behind a prologue stay with k_conv.hip)
-    if constexpr (NTW == 0) { if (stats) C3S_GO(true, true); else C3S_GO(false, true); }
-    else return 0;
-  } else { if (stats) C3S_GO(true, false); else C3S_GO(false, false); }
+#define C3S_GO(S, M) MDS_LAUNCH((c3s_kernel<CIN, NF, NSPL, SPW, NPW, NSW, S, M, NTW>), grid, block, smem, stream, g)
+  if (!masked) { if (stats) C3S_GO(true, false); else C3S_GO(false, false); }
+  else if constexpr (NTW == 0) { if (stats) C3S_GO(true, true); else C3S_GO(false, true); }      // (NTW > 0: whole bands, c3_fwd_route)
 #undef C3S_GO
-  return 1;
 }
 
-// the stride-2 forward layers (TF-SAME pads 0 / 1, even extents): taps (ky, kx) in 0..2 from the input pixel (2 oy, 2 ox)
-static int c3s_try(const mds_conv_fwd_args* a, mds_stream_t stream) {
-  const bool pro = a->pro.mode == MDS_PRO_BN_SILU;
-  if (a->dtype != MDS_BF16 || a->os != 1 || a->ntaps != 9 || a->ngroups > 1 || a->residual || a->post.mode != MDS_POST_NONE) return 0;
-  if ((a->pro.mode != MDS_PRO_NONE && !pro) || a->epi.mode != MDS_EPI_NONE || (pro && !(a->pro.scale && a->pro.shift))) return 0;
-  if ((mds_knob(MDS_KNOB_C3_DBG) & 64)) return 0;      // A/B: the stride-2 forward layers through k_conv.hip
-  if (a->IH % 2 || a->IW % 2 || a->OH != a->IH / 2 || a->OW != a->IW / 2 || a->A != a->OH || a->B != a->OW || a->oy0 || a->ox0) return 0;
-  if ((long)a->IH * a->IW * a->Cin >= (1L << 30) || (long)a->OH * a->OW * a->Cout >= (1L << 30)) return 0;
-  int tapw[9];
-  for (int t = 0; t < 9; ++t) tapw[t] = -1;
-  for (int t = 0; t < 9; ++t) {
-    if (a->dy[t] < 0 || a->dy[t] > 2 || a->dx[t] < 0 || a->dx[t] > 2) return 0;
-    tapw[3 * a->dy[t] + a->dx[t]] = a->wi[t];
+// the kernel, instance and tap map of an mds_conv_fwd launch
+static C3Route<mds_conv_fwd_args> c3_fwd_route(const mds_conv_fwd_args* a) {
+  C3Route<mds_conv_fwd_args> r = {};
+  const int knob = mds_knob(MDS_KNOB_C3);
+  const bool res = a->residual != nullptr, stats = a->stats != nullptr, post = a->post.mode != MDS_POST_NONE, pro = a->pro.mode == MDS_PRO_BN_SILU;
+  const bool small = (long)a->N * a->OH * a->OW < 16384 && knob != 2;      // small launches (inference, tests of the old kernels): k_conv.hip
+  const mds_poststat_t& ps = a->post;      // post statistics as these kernels take them: PLAIN, SILU, or MASK with one factor per image
+  if (post && !((ps.mode == MDS_POST_PLAIN || ps.mode == MDS_POST_SILU || (ps.mode == MDS_POST_MASK && ps.mask && ps.rows_per_group == (long)a->OH * a->OW))
+                && ps.y && ps.bn && ps.stats)) return r;
+  if (knob == 1 || a->dtype != MDS_BF16 || a->ntaps != 9 || a->epi.mode != MDS_EPI_NONE) return r;
+  if ((a->pro.mode != MDS_PRO_NONE && !pro) || (pro && !(a->pro.scale && a->pro.shift))) return r;
+  if (a->ngroups == 4) {      // the stride-2 data gradient as engine._conv_dgrad launches it: the four output parities as tap groups
+    if (a->is != 1 || a->os != 2 || pro || res || stats) return r;
+    if ((a->OH != 2 * a->IH && a->OH != 2 * a->IH - 1) || (a->OW != 2 * a->IW && a->OW != 2 * a->IW - 1)) return r;
+    if ((long)a->OH * a->OW * (a->Cin > a->Cout ? a->Cin : a->Cout) >= (1L << 30)) return r;
+    for (int gi = 0; gi < 4; ++gi) if ((a->g_oy0[gi] | a->g_ox0[gi]) & ~1) return r;
+    if (!c3_tapmap(r.tapw, a->dy, a->dx, a->wi, a->wtaps, 0, 4, a->g_ntaps, a->g_oy0, a->g_ox0) || small) return r;
+    if (a->Cin == 128 && a->Cout == 32) r.launch = post ? c3t_launch<128, 1, 2, 3, 1, true> : c3t_launch<128, 1, 2, 3, 1, false>;
+    if (a->Cin == 64 && a->Cout == 16) r.launch = post ? c3t_launch<64, 1, 1, 2, 2, true> : c3t_launch<64, 1, 1, 2, 2, false>;
+    return r;
   }
-  for (int t = 0; t < 9; ++t) if (tapw[t] < 0 || tapw[t] >= a->wtaps) return 0;
-  if ((long)a->N * a->OH * a->OW < 16384 && mds_knob(MDS_KNOB_C3) != 2) return 0;
-  if (a->Cin == 32 && a->Cout == 128 && !pro) return c3s_launch<32, 2, 4, 2, 2, 2, 0>(a, tapw, stream);      // blocks.2.0
-  if (a->Cin == 16 && a->Cout == 64 && !pro) return c3s_launch<16, 2, 2, 2, 2, 2, 0>(a, tapw, stream);
-  if (a->Cin == 16 && a->Cout == 64 && pro) return c3s_launch<16, 1, 4, 4, 1, 1, 6>(a, tapw, stream);        // blocks.1.0: reads blocks.0.0's raw output
-  return 0;
-}
-
-// 1 = launched, 0 = not a shape of this kernel (the caller goes on to k_conv.hip's kernels)
-int c3_try(const mds_conv_fwd_args* a, mds_stream_t stream) {
-  if (mds_knob(MDS_KNOB_C3) == 1) return 0;
-  if (a->ngroups == 4) return c3t_try(a, stream);
-  if (a->is == 2) return c3s_try(a, stream);
-  if (a->dtype != MDS_BF16 || a->is != 1 || a->os != 1 || a->ntaps != 9 || a->ngroups > 1) return 0;
-  const bool pro = a->pro.mode == MDS_PRO_BN_SILU;
-  if ((a->pro.mode != MDS_PRO_NONE && !pro) || a->epi.mode != MDS_EPI_NONE || !c3_post_ok(a)) return 0;
-  if (pro && (mds_knob(MDS_KNOB_C3_DBG) & 32)) return 0;      // A/B: the first 3x3 layer through k_conv.hip
-  if (pro && !(a->Cin == 32 && a->Cout == 16 && !a->residual && a->post.mode == MDS_POST_NONE && a->pro.scale && a->pro.shift)) return 0;
-  if (a->A != a->OH || a->B != a->OW || a->OH != a->IH || a->OW != a->IW || a->oy0 || a->ox0) return 0;
-  if ((long)a->IH * a->IW * (a->Cin > a->Cout ? a->Cin : a->Cout) >= (1L << 30)) return 0;
-  int tapw[9];
-  for (int t = 0; t < 9; ++t) tapw[t] = -1;
-  for (int t = 0; t < 9; ++t) {
-    if (a->dy[t] < -1 || a->dy[t] > 1 || a->dx[t] < -1 || a->dx[t] > 1) return 0;
-    tapw[3 * (a->dy[t] + 1) + a->dx[t] + 1] = a->wi[t];
+  if (a->is == 2) {      // the stride-2 forward layers (TF-SAME pads 0 / 1, even extents): taps (ky, kx) in 0..2 from input pixel (2 oy, 2 ox)
+    if (a->os != 1 || a->ngroups > 1 || res || post) return r;
+    if (a->IH % 2 || a->IW % 2 || a->OH != a->IH / 2 || a->OW != a->IW / 2 || a->A != a->OH || a->B != a->OW || a->oy0 || a->ox0) return r;
+    if ((long)a->IH * a->IW * a->Cin >= (1L << 30) || (long)a->OH * a->OW * a->Cout >= (1L << 30)) return r;
+    if (!c3_tapmap(r.tapw, a->dy, a->dx, a->wi, a->wtaps, C3_S2) || small) return r;
+    if (a->Cin == 32 && a->Cout == 128 && !pro) r.launch = c3s_launch<32, 2, 4, 2, 2, 2, 0>;      // blocks.2.0
+    if (a->Cin == 16 && a->Cout == 64 && !pro) r.launch = c3s_launch<16, 2, 2, 2, 2, 2, 0>;
+    // blocks.1.0 reads blocks.0.0's raw output: whole 64-column bands only (the transform-wave form runs three waves per SIMD - 168
+    // VGPRs - and its column-masked statistics variant spills 34 of them: ragged widths behind a prologue stay with k_conv.hip)
+    if (a->Cin == 16 && a->Cout == 64 && pro && a->OW % 64 == 0) r.launch = c3s_launch<16, 1, 4, 4, 1, 1, 6>;
+    return r;
   }
-  for (int t = 0; t < 9; ++t) if (tapw[t] < 0 || tapw[t] >= a->wtaps) return 0;
-  const long rows = (long)a->N * a->IH * a->IW;
-  if (rows < 16384 && mds_knob(MDS_KNOB_C3) != 2) return 0;      // small launches (inference, tests of the old kernels): k_conv.hip
+  if (a->is != 1 || a->os != 1 || a->ngroups > 1 || (stats && (res || post))) return r;      // (statistics never meet a residual / post sums)
+  if (a->A != a->OH || a->B != a->OW || a->OH != a->IH || a->OW != a->IW || a->oy0 || a->ox0) return r;
+  if ((long)a->IH * a->IW * (a->Cin > a->Cout ? a->Cin : a->Cout) >= (1L << 30)) return r;
+  if (!c3_tapmap(r.tapw, a->dy, a->dx, a->wi, a->wtaps, C3_S1) || small) return r;
   // helper waves: the data gradients read wide rows and write narrow ones (three DMA waves, one store wave); the forward layers two and two
-  const bool alt = (mds_knob(MDS_KNOB_C3_DBG) & 16) != 0;      // A/B: the other split
-  if (a->Cin == 128 && a->Cout == 32) return alt ? c3_launch<128, 1, 2, 1, 2, 2>(a, tapw, stream) : c3_launch<128, 1, 2, 1, 3, 1>(a, tapw, stream);
-  if (pro) return c3_launch<32, 1, 1, 1, 1, 1, false, 8>(a, tapw, stream);      // the first 3x3 layer: BN + SiLU of the stem's output on the way in
-  if (a->Cin == 48 && a->Cout == 192) return c3_launch<48, 2, 2, 1, 2, 2>(a, tapw, stream);      // three passes of 64 channels: a 96-channel slice per wave pair does not fit the registers
-  if (a->Cin == 16 && a->Cout == 32) return c3_launch<16, 2, 1, 1, 2, 2>(a, tapw, stream);      // (one DMA wave + three store waves for the POST_SILU form: 12.89 vs 12.15 ms per step - the ring starves)
-  if (a->Cin == 32 && a->Cout == 128) return alt ? c3_launch<32, 2, 4, 2, 1, 3>(a, tapw, stream) : c3_launch<32, 2, 4, 2, 2, 2>(a, tapw, stream);
-  return 0;
+  if (pro && a->Cin == 32 && a->Cout == 16) r.launch = c3_pick<C3_PLAIN, 32, 1, 1, 1, 1, 1, false, 8>(res, post);      // the first 3x3 layer: BN + SiLU of the stem's output on the way in
+  if (pro) return r;
+  if (a->Cin == 128 && a->Cout == 32) r.launch = c3_pick<C3_ALL, 128, 1, 2, 1, 3, 1>(res, post);
+  if (a->Cin == 48 && a->Cout == 192) r.launch = c3_pick<C3_ALL, 48, 2, 2, 1, 2, 2>(res, post);      // three passes of 64 channels: a 96-channel slice per wave pair does not fit the registers
+  if (a->Cin == 16 && a->Cout == 32) r.launch = c3_pick<C3_ALL, 16, 2, 1, 1, 2, 2>(res, post);      // (one DMA wave + three store waves for the POST_SILU form: 12.89 vs 12.15 ms per step - the ring starves)
+  if (a->Cin == 32 && a->Cout == 128) r.launch = c3_pick<C3_ALL & ~C3_RESPOST, 32, 2, 4, 2, 2, 2>(res, post);      // (a residual + post ring passes the LDS cap)
+  return r;
 }
 
-// what the planner asks before it folds a BatchNorm backward's sums into a 3x3 data gradient (engine._conv_dgrad): does the
-// launch - forward shape N x IH x IW x Cin -> Cout at `stride` - go to one of the kernels above that implement `post`?
+int c3_try(const mds_conv_fwd_args* a, mds_stream_t stream) { return c3_go(c3_fwd_route(a), a, stream); }      // 1 = launched, 0 = k_conv.hip's kernels
+
+// what the planner asks before it folds a BatchNorm backward's sums into a 3x3 data gradient: does the launch engine._conv_dgrad makes for
+// the forward layer N x IH x IW x Cin -> Cout at `stride` route to a kernel above with post statistics?  That launch, rebuilt here: extents
+// and channels swapped; stride 1: the taps of geometry.taps_dgrad_s1; stride 2: the four parity groups of geometry.taps_dgrad_s2 at the
+// TF-SAME pads (IH % 2, IW % 2) if Cout % 32 == 0, else four launches without post statistics.  Precondition: the engine's taps are those.
 extern "C" int mds_conv_dgrad_post_ok(int dtype, int N, int IH, int IW, int Cin, int Cout, int stride, int has_residual) {
-  if (dtype != MDS_BF16 || mds_knob(MDS_KNOB_C3) == 1) return 0;
-  if ((long)N * IH * IW < 16384 && mds_knob(MDS_KNOB_C3) != 2) return 0;
-  if (stride == 1) return (Cout == 128 && Cin == 32) || (!has_residual && Cout == 16 && Cin == 32);      // c3_kernel<128 -> 32> / <16 -> 32>
-  if (stride == 2) return !has_residual && IH % 2 == 0 && IW % 2 == 0 && ((Cout == 128 && Cin == 32) || (Cout == 64 && Cin == 16));
-  return 0;
+  static const double dummy = 0;      // the route looks at the post pointers, never through them
+  if (stride != 1 && (stride != 2 || Cout % 32)) return 0;
+  mds_conv_fwd_args c = {};
+  c.dtype = dtype; c.N = N; c.OH = IH; c.OW = IW; c.Cin = Cout; c.Cout = Cin; c.is = 1; c.ntaps = 9; c.wtaps = 9; c.residual = has_residual ? &dummy : nullptr;
+  c.post.mode = MDS_POST_PLAIN; c.post.y = c.post.bn = (const float*)&dummy; c.post.stats = (double*)&dummy;
+  if (stride == 1) {
+    c.IH = c.A = IH; c.IW = c.B = IW; c.os = 1;
+    for (int k = 0; k < 9; ++k) { c.dy[k] = k / 3 - 1; c.dx[k] = k % 3 - 1; c.wi[k] = k; }
+  } else {
+    c.IH = c.A = (IH + 1) / 2; c.IW = c.B = (IW + 1) / 2; c.os = 2; c.ngroups = 4;
+    for (int gi = 0, t = 0; gi < 4; ++gi) {
+      c.g_oy0[gi] = gi / 2; c.g_ox0[gi] = gi % 2; c.g_A[gi] = (IH - gi / 2 + 1) / 2; c.g_B[gi] = (IW - gi % 2 + 1) / 2;
+      for (int k = 0, ey, ex; k < 9; ++k)
+        if ((ey = gi / 2 + IH % 2 - k / 3) % 2 == 0 && (ex = gi % 2 + IW % 2 - k % 3) % 2 == 0) { c.dy[t] = ey / 2; c.dx[t] = ex / 2; c.wi[t++] = 8 - k; ++c.g_ntaps[gi]; }
+    }
+  }
+  return c3_fwd_route(&c).launch != nullptr;
 }
 
 // mds_pw_fwd's large prologue-free bf16 launches (the edge-residual projections' data gradients: 0.3 - 1.2 M rows, 32 / 48 -> 64 ... 192
 // channels) as 1x1 "images" of W-pixel rows through c3_kernel<..., ONE>.  1 = launched, 0 = not one of these.
 int c3_pw_try(const mds_pw_fwd_args* a, mds_stream_t stream) {
-  if (mds_knob(MDS_KNOB_C3) == 1 || a->dtype != MDS_BF16) return 0;
+  if (mds_knob(MDS_KNOB_C3) == 1 || a->dtype != MDS_BF16 || (a->M < 262144 && mds_knob(MDS_KNOB_C3) != 2)) return 0;
   if (a->pro.mode != MDS_PRO_NONE || a->epi.mode != MDS_EPI_NONE || a->post.mode != MDS_POST_NONE || a->stats || a->split > 1) return 0;
-  if (a->M < 262144 && mds_knob(MDS_KNOB_C3) != 2) return 0;
-  const bool k32 = a->K == 32 && (a->N == 64 || a->N == 128), k48 = a->K == 48 && a->N % 64 == 0 && a->N <= 192;
-  if (!k32 && !k48) return 0;
-  int W = 0;
+  if (!(a->K == 32 && (a->N == 64 || a->N == 128)) && !(a->K == 48 && a->N % 64 == 0 && a->N <= 192)) return 0;
+  int W = 0;      // a multiple of 32: whole bands
   for (int w = 640; w >= 32; w -= 32) if (a->M % w == 0 && a->M / w >= 3) { W = w; break; }
   if (!W || a->M * (a->N > a->K ? a->N : a->K) >= (1L << 30)) return 0;
   mds_conv_fwd_args c = {};
   c.dtype = a->dtype; c.N = 1; c.IH = c.OH = c.A = (int)(a->M / W); c.IW = c.OW = c.B = W; c.Cin = a->K; c.Cout = a->N;
   c.os = c.is = 1; c.ntaps = 9; c.wtaps = 1; c.x = a->x; c.w = a->w; c.y = a->y; c.residual = a->residual;
-  const int tapw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (a->K == 32 && a->N == 128) return c3_launch<32, 2, 4, 2, 1, 3, true>(&c, tapw, stream);
-  if (a->K == 32) return c3_launch<32, 2, 2, 1, 1, 3, true>(&c, tapw, stream);
-  return c3_launch<48, 2, 2, 1, 1, 3, true>(&c, tapw, stream);
+  C3Route<mds_conv_fwd_args> r = {};      // every tap is the centre one: weight slot 0
+  if (a->K == 48) r.launch = c3_pick<C3_PLAIN | C3_RES, 48, 2, 2, 1, 1, 3, true>(a->residual, false);
+  else if (a->N == 128) r.launch = c3_pick<C3_PLAIN | C3_RES, 32, 2, 4, 2, 1, 3, true>(a->residual, false);
+  else r.launch = c3_pick<C3_PLAIN | C3_RES, 32, 2, 2, 1, 1, 3, true>(a->residual, false);
+  return c3_go(r, &c, stream);
 }

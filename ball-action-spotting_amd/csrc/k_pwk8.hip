@@ -462,8 +462,7 @@ int pw_fwd_k_try(const mds_pw_fwd_args* a, mds_stream_t stream) {
   // one block per CU (512 threads, ~200 VGPRs), so the launch runs in ceil(blocks / 256) rounds - the smallest rounds * BM wins
   // (18 400 rows: 80-row tiles, 230 blocks, one round; 73 600 rows: 96-row tiles, 767 blocks, three rounds)
   const int shape = N > 128 ? 0 : (N > 96 ? 1 : 2);
-  static int cus = 0;      // one block per CU: the tile-height rule counts rounds of the chip
-  if (cus == 0) cus = mds_cu_count();
+  const int cus = mds_cu_count();      // one block per CU: the tile-height rule counts rounds of the chip
   auto cost = [&](int bm) { const long blocks = cdiv(a->M, bm); return (long)cdiv(blocks, cus) * bm; };
   int BM;
   if (shape == 2) BM = 96;

@@ -161,9 +161,15 @@ MDS_DEV void sreg_pin(f32x8& v) { asm volatile("" : "+s"(v)); }
 // neither a vector register per lane nor an entry on vmcnt
 MDS_DEV float ld_uniform(const float* p, int idx) { return ((const __attribute__((address_space(4))) float*)(uintptr_t)p)[idx]; }
 
-// CUs of the current device (launch-shape rules that count rounds of the chip ask once)
+// CUs of the current device (launch-shape rules that count rounds of the chip), asked once per device id; racing first
+// askers store the same value
 inline int mds_cu_count() {
+  static std::atomic<int> cache[64];
   int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  const bool cached = dev >= 0 && dev < 64;
+  if (cached && (n = cache[dev].load(std::memory_order_relaxed)) > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  if (cached) cache[dev].store(n, std::memory_order_relaxed);
   return n;
 }

@@ -360,6 +360,46 @@ def test_c3_post_statistics(be, stride, N, H, W, blocks, masked, Cin, Cout):
         be.lib.fn["dev_set"](cabi.MDS_KNOB_C3, 0)
 
 
+@pytest.mark.parametrize("knob", [0, 1, 2])
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+@pytest.mark.parametrize("res", [False, True])
+@pytest.mark.parametrize("H,W", [(6, 10), (7, 9)])
+@pytest.mark.parametrize("Cin,Cout,stride", [(32, 128, 1), (32, 16, 1), (48, 192, 1), (32, 128, 2), (16, 64, 2)])
+def test_conv_dgrad_post_ok_matches_the_launch(be, knob, dt, res, H, W, Cin, Cout, stride):
+    """mds_conv_dgrad_post_ok says 1 exactly when the data-gradient launch engine._conv_dgrad makes (its real taps, extents swapped,
+    the residual flag) takes post statistics: mds_conv_fwd with `post` succeeds instead of refusing it"""
+    code, tdt = DT[dt]                        # (Cin, Cout: the forward layer)
+    N = 1
+    OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
+    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, Cin, device=be.device, dtype=torch.float64)
+    bn = torch.stack([torch.ones(Cin), torch.zeros(Cin), torch.zeros(Cin), torch.ones(Cin)])
+    post = cabi.make("mds_poststat_t", mode=1, y=be.t(torch.zeros(N, H, W, Cin).to(tdt)), bn=be.t(bn), mask=None, rows_per_group=H * W, stats=st)
+    common = dict(dtype=code, N=N, IH=OH, IW=OW, Cin=Cout, OH=H, OW=W, Cout=Cin, wtaps=9, x=be.t(torch.randn(N, OH, OW, Cout).to(tdt)),
+                  w=be.t(torch.randn(Cin, 9, Cout).to(tdt)), y=be.t(torch.zeros(N, H, W, Cin).to(tdt)), pro=cabi.pro(0),
+                  residual=be.t(torch.zeros(N, H, W, Cin).to(tdt)) if res else None, stats=None, post=post)
+    if stride == 1:
+        dy, dx, wi = geo.taps_dgrad_s1()
+        args = cabi.make("mds_conv_fwd_args", A=H, B=W, oy0=0, ox0=0, os=1, **{"is": 1}, ntaps=9, dy=dy, dx=dx, wi=wi, **common)
+    else:
+        par = [(py, px, *geo.taps_dgrad_s2(py, px, pt, pl), (H - py + 1) // 2, (W - px + 1) // 2) for py in range(2) for px in range(2)]
+        args = cabi.make("mds_conv_fwd_args", A=max(p[5] for p in par), B=max(p[6] for p in par), oy0=0, ox0=0, os=2, **{"is": 1},
+                         ntaps=sum(len(p[2]) for p in par), dy=sum((p[2] for p in par), []), dx=sum((p[3] for p in par), []),
+                         wi=sum((p[4] for p in par), []), ngroups=4, g_ntaps=[len(p[2]) for p in par],
+                         g_oy0=[p[0] for p in par], g_ox0=[p[1] for p in par], g_A=[p[5] for p in par], g_B=[p[6] for p in par], **common)
+    be.lib.check(be.lib.fn["dev_set"](cabi.MDS_KNOB_C3, knob), "dev_set")
+    try:
+        ok = be.lib.fn["conv_dgrad_post_ok"](code, N, H, W, Cin, Cout, stride, int(res))
+        try:
+            be.call("conv_fwd", args)
+            be.sync()
+            ran = 1
+        except cabi.MdsError:
+            ran = 0
+    finally:
+        be.lib.fn["dev_set"](cabi.MDS_KNOB_C3, 0)
+    assert ok == ran
+
+
 @pytest.mark.parametrize("N,H,W,blocks", [(2, 13, 128, 0), (1, 21, 70, 2), (1, 40, 64, 1), (1, 2, 64, 0)])
 def test_c3_prologue_through_transform_waves(be, N, H, W, blocks):
     """the first 3x3 layer (32 -> 16, input = the stem's raw output read through BatchNorm + SiLU): k_c3.hip's transform waves rewrite

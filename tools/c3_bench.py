@@ -1,5 +1,5 @@
-"""Developer tool: the stride-1 3x3 layers through k_c3.hip alone, with its ablation bits (MDS_KNOB_C3_DBG) - which phase binds?
-   python tools/c3_bench.py [dbg values ...]        (default: 0 1 2 4 8 3 6 7 15)"""
+"""Developer tool: the 3x3 layers through k_c3.hip alone against k_conv.hip, beside their HBM / MFMA floors.
+   python tools/c3_bench.py        (ablations: C3_LIB=libmds_c3abl<n>.so.bin from `make c3abl ABL=n` - which phase binds?)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ball-action-spotting_amd")]
@@ -32,7 +32,6 @@ def timeit(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-dbgs = [int(v) for v in sys.argv[1:]] or [0, 1, 2, 4, 8, 3, 6, 7, 15]
 for (N, H, W, Cin, Cout, res, stats, tag) in SHAPES:
     stride = 2 if " s2 " in tag else 1
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
@@ -50,13 +49,9 @@ for (N, H, W, Cin, Cout, res, stats, tag) in SHAPES:
     s = torch.cuda.current_stream().cuda_stream
     flops = 2 * N * OH * OW * 9 * Cin * Cout
     nbytes = (x.numel() + y.numel() * (2 if res else 1)) * 2
-    out = []
     lib.fn["dev_set"](cabi.MDS_KNOB_C3, 1)
     t_old = timeit(lambda: lib.call("conv_fwd", a, s))
     lib.fn["dev_set"](cabi.MDS_KNOB_C3, 0)
-    for d in dbgs:
-        lib.fn["dev_set"](cabi.MDS_KNOB_C3_DBG, d)
-        out.append((d, timeit(lambda: lib.call("conv_fwd", a, s))))
-    lib.fn["dev_set"](cabi.MDS_KNOB_C3_DBG, 0)
-    print(f"{tag:28s} k_conv {t_old:7.1f} us | " + "  ".join(f"dbg{d}: {t:6.1f}" for d, t in out) +
+    t_c3 = timeit(lambda: lib.call("conv_fwd", a, s))
+    print(f"{tag:28s} k_conv {t_old:7.1f} us | k_c3 {t_c3:7.1f} us" +
           f" | floor: HBM {nbytes / 5e6:.0f} us at 5 TB/s, MFMA {flops / 2.5e9:.0f} us at peak", flush=True)
