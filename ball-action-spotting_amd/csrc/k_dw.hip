@@ -1264,7 +1264,10 @@ static dim3 dw_grid(DwStrips& g) {
   return g.swap == 1 ? dim3(g.nchunks, sb) : dim3(sb, g.nchunks);
 }
 
+int dw_fwd_expand(const mds_dw_fwd_args* a, mds_stream_t stream);   // k_dwx.hip: the launch with an expansion prologue
+
 extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
+  if (a && a->expand.x) return dw_fwd_expand(a, stream);
   MDS_REQUIRE(a && a->N > 0 && a->T > 0 && a->C % 8 == 0, "dw_fwd: bad dims");
   MDS_REQUIRE(a->kt == 1 || a->kt == 3, "dw_fwd: kt must be 1 or 3");
   MDS_REQUIRE(a->stride == 1 || a->stride == 2, "dw_fwd: stride");

@@ -161,6 +161,11 @@ def op_cost(name, kw, es):
         px = g("N") * g("OH") * g("OW")
         nwide = 2 if g("dyp") else 1      # dy formed on load (mds_dyp_t): the gradient source u AND the raw stem output y are read
         return g("N") * 3 * g("H") * g("W") * 4 + nwide * px * g("Cout") * es, 2 * 27 * g("Cout") * px
+    if name == "dw_fwd" and g("expand"):
+        ex = g("expand")             # the narrow block input is read, the expansion computed in the launch (mds_expand_t)
+        nin = g("N") * g("IH") * g("IW") * ex["cin"]
+        nout = g("N") * g("OH") * g("OW") * g("C")
+        return (nin + nout) * es + g("C") * ex["cin"] * es, 2 * 9 * nout + 2 * g("N") * g("IH") * g("IW") * ex["cin"] * g("C")
     if name == "dw_fwd":
         nin = g("N") * g("T") * g("IH") * g("IW") * g("C")
         nout = g("N") * g("T") * g("OH") * g("OW") * g("C")
@@ -198,7 +203,7 @@ def _hip_path():
 class Plan:
     """The recorded schedules + buffers for one configuration."""
 
-    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None):
+    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False):
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
                                     # tail plans: ("probs", tta) - the head also writes the TTA-mean of the sigmoids (mds.predict)
@@ -221,6 +226,9 @@ class Plan:
         self.fuse_bn_bwd = os.environ.get("MDS_FUSE_BN_BWD", "1") != "0" and code == cabi.MDS_BF16
         # inference plans (eval-mode BatchNorm, no gradient): producers store activated outputs (mds_epi_t)
         self.eval_epilogues = (not training) and (not need_grad) and os.environ.get("MDS_EVAL_EPI", "1") == "1"
+        # MultiDimStacker.eval_fusion: the 2D inverted-residual blocks of an inference plan expand their input inside the
+        # depthwise launch (mds_expand_t) - no mid-wide y1 tensor, no expansion pw_fwd
+        self.eval_fusion = bool(eval_fusion) and self.eval_epilogues
         self.in_flight = False
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
@@ -495,9 +503,14 @@ class Plan:
             bn.finalize(self, fseg)         # -> the plan's eval-BatchNorm table (one launch per forward)
         def epi(bn, mode):
             return dict(_struct="mds_epi_t", mode=mode, scale=bn.scale, shift=bn.shift)
-        a1 = self.act(Min, mid)
-        self.op(fseg, "pw_fwd", dtype=self.code, M=Min, K=cin, N=mid, x=xin, w=self.pack(blk.conv_pw.weight, cabi.MDS_PACK_OI, mid, cin, 1),
-                y=a1, pro=dict(mode=0), residual=None, stats=None, epi=epi(bn1, EPI_BN_SILU), **self._split(Min, cin, mid))
+        w1 = self.pack(blk.conv_pw.weight, cabi.MDS_PACK_OI, mid, cin, 1)
+        if self.eval_fusion and kt == 1 and T == 1 and mid % 16 == 0 and cin % 8 == 0:
+            # the expansion runs inside the depthwise launch: y1 = silu(bn1(xin w1^T)) lives in LDS only (k_dwx.hip)
+            a1, expand = None, dict(_struct="mds_expand_t", x=xin, w=w1, cin=cin, scale=bn1.scale, shift=bn1.shift)
+        else:
+            a1, expand = self.act(Min, mid), None
+            self.op(fseg, "pw_fwd", dtype=self.code, M=Min, K=cin, N=mid, x=xin, w=w1, y=a1, pro=dict(mode=0), residual=None,
+                    stats=None, epi=epi(bn1, EPI_BN_SILU), **self._split(Min, cin, mid))
         a2 = self.act(Mout, mid)
         R = blk.se.rd
         pooled, hidden, gate = self.zero_fwd64(groups * mid), self.f32(groups * R), self.f32(groups * mid)
@@ -505,7 +518,8 @@ class Plan:
         fuse_pool = groups == N and os.environ.get("MDS_EVAL_POOL", "1") == "1"
         self.op(fseg, "dw_fwd", dtype=self.code, N=N, T=T, IH=IH, IW=IW, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt,
                 pad_l=pl, kt=kt, x=a1, w=P(blk.conv_dw.weight), y=a2, pro=dict(mode=0), stats=None, epi=epi(bn2, EPI_BN_SILU),
-                pool=pooled if fuse_pool else None, pool_inv=1.0 / rpg if fuse_pool else 0.0)
+                pool=pooled if fuse_pool else None, pool_inv=1.0 / rpg if fuse_pool else 0.0,
+                **({"expand": expand} if expand is not None else {}))
         if not fuse_pool:
             self.op(fseg, "se_pool", dtype=self.code, groups=groups, rows_per_group=rpg, C=mid, y=a2, scale=None, shift=None,
                     pooled=pooled, act=None)

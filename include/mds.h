@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 132
+#define MDS_VERSION 133
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -300,6 +300,20 @@ typedef struct {
 } mds_stem_wgrad_args;
 int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream);
 
+/* ---- expansion prologue of the 2D depthwise forward (inference plans; mds_dw_fwd_args.expand): the block's narrow
+ * input x is expanded in the same launch, y1 = silu((x * w^T)[c] * scale[c] + shift[c]), one tile of output pixels and
+ * 64 channels at a time into LDS - the mid-wide y1 of an inverted-residual block is never written to memory.  Zero
+ * padding applies to the ACTIVATED y1 (a padded tap reads 0).  fp32: split-bf16 products (three bf16 MFMAs per
+ * fragment pair, fp32 accumulation); bf16: one bf16 MFMA.  Needs T == 1, kt == 1, an output transform, no prologue,
+ * no statistics, C % 16 == 0, cin % 8 == 0; `x` of mds_dw_fwd_args is then unused.  x == NULL: off.          */
+typedef struct {
+  const void* x;        /* [N][IH][IW][cin] activated block input, storage dtype */
+  const void* w;        /* [C][cin] expansion filter (MDS_PACK_OI, taps = 1), storage dtype */
+  int cin;
+  const float* scale;   /* [C] BatchNorm of the expansion (eval table) */
+  const float* shift;   /* [C] */
+} mds_expand_t;
+
 /* ---- K5/K6: depthwise 3x3 (2D, stride 1 or TF-SAME stride 2) and 3x3x3 (3D, pad 1).
  * Input is the raw output of the preceding 1x1 conv read through a BN+SiLU prologue.
  * replaces timm InvertedResidual.conv_dw and multidim_stacker.py:110-113.
@@ -321,6 +335,7 @@ typedef struct {
    * Needs an output transform, a sliding-window kernel, and kt == 3 or T == 1 (group = batch element n).        */
   double* pool;        /* optional fp64 [N][C], caller-zeroed */
   float pool_inv;      /* 1 / (T*OH*OW) */
+  mds_expand_t expand; /* optional expansion prologue (expand.x != NULL): the depthwise input is computed in the launch */
 } mds_dw_fwd_args;
 int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream);
 
