@@ -13,7 +13,7 @@
 // In both, BatchNorm sums and filter gradients are reduced in the block (shuffles / LDS) and written
 // with coalesced atomics in the parameter's own order.
 #include <stdlib.h>
-#include "elem.h"
+#include "se_tail.h"
 
 template <typename T> struct DwCfg { static const int CC = 128 / sizeof(T); };  // channels per slab
 
@@ -261,12 +261,17 @@ MDS_DEV f32x2 epi2(f32x2 v, int mode, f32x2 sc, f32x2 sh) {
   return mode == MDS_EPI_BN_SILU ? v * sigmoid2(v) : v;
 }
 
+#define DW_SE_RH 4   // rows of w1 in flight per wave in the squeeze-excite tail (se_tail.h): 100 VGPRs of loads, under every host kernel's own count
 struct DwStrips { int nchunks, nseg, L, nbands, spt, swap; long nstrips; };
 
 // Squeeze-excite pooling of an inference plan inside the producing pass (mds_dw_fwd_args.pool): `sp` is this thread's sum of
 // the STORED outputs of its strip (what mds_se_pool would read back), `img` the strip's batch element.  The 8 strips of a block
 // are reduced in LDS; a block whose strips straddle two images flushes once per image.
-MDS_DEV void dw_pool_flush(float (&red)[8][4][32], f32x2 sp, int img, bool strip_ok, double* pool, float inv, int C, int cbeg) {
+// SE_RH > 0: the launch carries the squeeze-excite tail (mds_se_tail_t, se_tail.h) - after its flush the block takes the tickets of
+// its images and computes the gate of every image it completes; `per_image` = strips per image x channel chunks.
+template <int SE_RH = 0>
+MDS_DEV void dw_pool_flush(float (&red)[8][4][32], f32x2 sp, int img, bool strip_ok, double* pool, float inv, int C, int cbeg,
+                           const mds_se_tail_t* se = nullptr, int per_image = 0) {
   __shared__ int img_s[8];
   const int tid = threadIdx.x, cp = tid & 31, sl = tid >> 5;
   red[sl][0][cp] = sp[0]; red[sl][1][cp] = sp[1];
@@ -286,6 +291,7 @@ MDS_DEV void dw_pool_flush(float (&red)[8][4][32], f32x2 sp, int img, bool strip
     }
     if (cur >= 0) atomicAdd(pool + (long)cur * C + cbeg + tid, (double)(t * inv));
   }
+  if (SE_RH > 0) se_tail_tickets<(SE_RH > 0 ? SE_RH : 1)>(*se, pool, C, img_s, per_image);
 }
 // Workgroup -> (strip block, channel chunk).  Consecutive workgroup ids go to consecutive XCDs (id % 8), each with its own L2.
 // Neighbouring strips share halo rows / columns ((R + 2) / R x (L + 2) / L = 1.5x the compulsory reads when every strip fetches
@@ -308,7 +314,7 @@ MDS_DEV DwBlock dw_block(const DwStrips& g) {
 #define MDS_DW2F_OCC 3   /* blocks per CU the bf16 / two-row variants of dw2_fwd are compiled for (library A/B) */
 #endif
 // POOL: the squeeze-excite pooling of inference plans (mds_dw_fwd_args.pool) - a template flag, so that the training kernels do not carry its sums
-template <typename T, int R, bool POOL = false>
+template <typename T, int R, int POOL = 0>   // POOL = 2: with the squeeze-excite tail
 // (fp32 six-row bands at 168 VGPRs spilled 56-63 registers: 1.3-1.5 TB/s in the fp32 inference plans; two blocks per CU for that variant)
 __global__ __launch_bounds__(256, (sizeof(T) == 4 && R == 6) ? 2 : MDS_DW2F_OCC) void dw2_fwd_kernel(mds_dw_fwd_args a, DwStrips g) {
   MDS_CHAIN_PRIO();
@@ -417,7 +423,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 && R == 6) ? 2 : MDS_DW2F_OCC)
       if (cbeg + c < C) atomicAdd(a.stats + ((long)(bx % MDS_STAT_SLOTS) * 2 + kk) * C + cbeg + c, (double)t);
     }
   }
-  if (POOL && a.pool) dw_pool_flush(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg);
+  if (POOL == 1 && a.pool) dw_pool_flush(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg);
+  if (POOL == 2) dw_pool_flush<DW_SE_RH>(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg, &a.se, g.nseg * g.nbands * g.nchunks);
 }
 
 // backward, same decomposition over INPUT pixels: window = dy rows iy-1..iy+R, cols ix-1..ix+1.
@@ -560,7 +567,7 @@ __global__ __launch_bounds__(256, 2) void dw2_bwd_kernel(mds_dw_bwd_args a, DwSt
 // row that needs it), the 27 taps of the channel pair are read from LDS once per column.  The LDS-tiled
 // kernel above had 216-324 blocks of five barrier-separated slices each for the whole launch.
 #define DW3_T 5
-template <typename T, bool POOL = false>
+template <typename T, int POOL = 0>   // POOL = 2: with the squeeze-excite tail
 __global__ __launch_bounds__(256, 2) void dw3_fwd_kernel(mds_dw_fwd_args a, DwStrips g) {
   MDS_CHAIN_PRIO();
   constexpr int TT = DW3_T;
@@ -680,7 +687,8 @@ __global__ __launch_bounds__(256, 2) void dw3_fwd_kernel(mds_dw_fwd_args a, DwSt
       if (cbeg + c < C) atomicAdd(a.stats + ((long)(bx % MDS_STAT_SLOTS) * 2 + kk) * C + cbeg + c, (double)t);
     }
   }
-  if (POOL && a.pool) dw_pool_flush(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg);
+  if (POOL == 1 && a.pool) dw_pool_flush(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg);
+  if (POOL == 2) dw_pool_flush<DW_SE_RH>(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg, &a.se, g.nseg * g.nbands * g.nchunks);
 }
 
 // ------------------------------------------------------------------------------------ 3x3x3, any T (time chunks)
@@ -969,7 +977,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 1 : MDS_DW3B_OCC) void dw3_bw
 // ------------------------------------------------------------------------------------ 3x3 stride 2 (TF-SAME)
 // Sliding window for the two stride-2 layers.  Forward: R = 3 output rows need 7 input rows; an output
 // column consumes two new input columns (window col 0 <- old col 2).
-template <typename T, bool POOL = false>
+template <typename T, int POOL = 0>   // POOL = 2: with the squeeze-excite tail
 __global__ __launch_bounds__(256, 3) void dw2s_fwd_kernel(mds_dw_fwd_args a, DwStrips g) {
   MDS_CHAIN_PRIO();
   constexpr int R = 3, NR = 2 * R + 1;
@@ -1070,7 +1078,8 @@ __global__ __launch_bounds__(256, 3) void dw2s_fwd_kernel(mds_dw_fwd_args a, DwS
       if (cbeg + c < C) atomicAdd(a.stats + ((long)(bx % MDS_STAT_SLOTS) * 2 + kk) * C + cbeg + c, (double)t);
     }
   }
-  if (POOL && a.pool) dw_pool_flush(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg);
+  if (POOL == 1 && a.pool) dw_pool_flush(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg);
+  if (POOL == 2) dw_pool_flush<DW_SE_RH>(red, sp, pimg, pok, a.pool, a.pool_inv, C, cbeg, &a.se, g.nseg * g.nbands * g.nchunks);
 }
 
 // Backward over INPUT pixels: a thread owns 4 input rows x pairs of input columns; the dy values that
@@ -1279,6 +1288,11 @@ extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
   MDS_REQUIRE((long)a->N * 64 < 65536, "dw_fwd: grid.z");
   MDS_REQUIRE(a->epi.mode == MDS_EPI_NONE || (a->epi.scale && a->epi.shift && !a->stats && (a->kt == 1 || a->T == DW3_T)),
               "dw_fwd: an output transform needs scale/shift, no statistics, and a sliding-window kernel (kt == 1, or T == %d)", DW3_T);
+  const bool se = a->se.gate != nullptr;
+  if (se) {   // (before the pooling rule: a missing pool / transform is reported as what the tail needs)
+    SE_TAIL_REQUIRE(a, "dw_fwd");
+    MDS_REQUIRE((a->kt == 1 && a->T == 1) || (a->kt == 3 && a->T == DW3_T), "dw_fwd: the squeeze-excite tail needs a sliding-window kernel");
+  }
   MDS_REQUIRE(!a->pool || (a->epi.mode != MDS_EPI_NONE && !a->stats && a->pool_inv > 0.f &&
                            ((a->kt == 1 && a->T == 1) || (a->kt == 3 && a->T == DW3_T))),
               "dw_fwd: pooling needs an output transform, no statistics, pool_inv, and a sliding-window kernel (kt == 1 with T == 1, or kt == 3 with T == %d)", DW3_T);
@@ -1293,7 +1307,10 @@ extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
     const int R = small ? 2 : 6;
     DwStrips g = dw_strips(images, a->OH, a->OW, a->C, R, dw2_len(images, a->OH, a->OW, a->C, R));
     dim3 grid = dw_grid(g), block(256);
-    if (a->pool) {
+    if (se) {
+      if (small) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 2, 2>), grid, block, 0, stream, *a, g));
+      else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 6, 2>), grid, block, 0, stream, *a, g));
+    } else if (a->pool) {
       if (small) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 2, true>), grid, block, 0, stream, *a, g));
       else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 6, true>), grid, block, 0, stream, *a, g));
     } else {
@@ -1305,14 +1322,16 @@ extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
   if (a->kt == 1 && a->stride == 2) {
     DwStrips g = dw_strips(a->N * a->T, a->OH, a->OW, a->C, 3);
     dim3 grid = dw_grid(g), block(256);
-    if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, true>), grid, block, 0, stream, *a, g));
+    if (se) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, 2>), grid, block, 0, stream, *a, g));
+    else if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, true>), grid, block, 0, stream, *a, g));
     else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, false>), grid, block, 0, stream, *a, g));
     return mds_check_launch("dw_fwd");
   }
   if (a->kt == 3 && a->T == DW3_T) {
     DwStrips g = dw_strips(a->N, a->OH, a->OW, a->C, 1, dw3_len(a->N, a->OH, a->OW, a->C, 20));
     dim3 grid = dw_grid(g), block(256);
-    if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, true>), grid, block, 0, stream, *a, g));
+    if (se) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, 2>), grid, block, 0, stream, *a, g));
+    else if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, true>), grid, block, 0, stream, *a, g));
     else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, false>), grid, block, 0, stream, *a, g));
     return mds_check_launch("dw_fwd");
   }

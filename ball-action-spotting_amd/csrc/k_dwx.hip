@@ -12,9 +12,11 @@
 // 41 KiB (stride 2), i.e. 5 / 3 blocks per CU by LDS.  fp32 x is split into hi / lo bf16 halves while it is staged
 // (split-bf16 product, Mma<float, true>: the numerics of the inference pw_fwd); bf16 runs one MFMA per fragment pair.
 #include "gemm.h"
+#include "se_tail.h"
 
 #define DWX_MC 64   // mid channels per block (4 waves x one 16-column MFMA tile)
 #define DWX_KC 32   // input channels per staged chunk (one MFMA k step)
+#define DWX_SE_RH 2 // rows of w1 in flight per wave in the squeeze-excite tail (se_tail.h): stays under the kernel's own ~100 VGPRs
 
 template <int S> struct DwxTile;
 template <> struct DwxTile<1> { static const int TOH = 8, TOW = 8; };
@@ -64,7 +66,7 @@ template <> struct DwxOp<float> {
   }
 };
 
-template <typename T, int S, bool POOL>
+template <typename T, int S, int POOL>   // POOL = 1: squeeze-excite pool, 2: pool + the squeeze-excite tail (mds_se_tail_t)
 __global__ __launch_bounds__(256) void dwx_fwd_kernel(mds_dw_fwd_args a, int tiles_x, int tiles_y, int nchunks) {
   MDS_CHAIN_PRIO();
   typedef DwxGeo<T, S> G;
@@ -186,6 +188,11 @@ __global__ __launch_bounds__(256) void dwx_fwd_kernel(mds_dw_fwd_args a, int til
       const float tot = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
       atomicAdd(a.pool + (long)n * C + c0 + tid, (double)(tot * a.pool_inv));
     }
+    if (POOL == 2) {   // a block is one (tile, channel chunk) of image n: one ticket each
+      __shared__ int se_img[8];
+      if (tid < 8) se_img[tid] = tid == 0 ? n : -1;
+      se_tail_tickets<DWX_SE_RH>(a.se, a.pool, C, se_img, tiles_x * tiles_y * nchunks);
+    }
   }
 }
 
@@ -194,8 +201,9 @@ static void dwx_launch(const mds_dw_fwd_args* a, mds_stream_t stream) {
   typedef DwxGeo<T, S> G;
   const int tiles_x = cdiv(a->OW, G::TOW), tiles_y = cdiv(a->OH, G::TOH), nchunks = cdiv(a->C, DWX_MC);
   const dim3 grid((unsigned)((long)a->N * tiles_y * tiles_x * nchunks)), block(256);
-  if (a->pool) MDS_LAUNCH((dwx_fwd_kernel<T, S, true>), grid, block, G::SMEM, stream, *a, tiles_x, tiles_y, nchunks);
-  else MDS_LAUNCH((dwx_fwd_kernel<T, S, false>), grid, block, G::SMEM, stream, *a, tiles_x, tiles_y, nchunks);
+  if (a->se.gate) MDS_LAUNCH((dwx_fwd_kernel<T, S, 2>), grid, block, G::SMEM, stream, *a, tiles_x, tiles_y, nchunks);
+  else if (a->pool) MDS_LAUNCH((dwx_fwd_kernel<T, S, 1>), grid, block, G::SMEM, stream, *a, tiles_x, tiles_y, nchunks);
+  else MDS_LAUNCH((dwx_fwd_kernel<T, S, 0>), grid, block, G::SMEM, stream, *a, tiles_x, tiles_y, nchunks);
 }
 
 // mds_dw_fwd with a->expand.x set (k_dw.hip routes here)
@@ -208,6 +216,7 @@ int dw_fwd_expand(const mds_dw_fwd_args* a, mds_stream_t stream) {
   MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE && !a->stats, "dw_fwd (expand): no prologue, no statistics");
   MDS_REQUIRE((a->epi.mode == MDS_EPI_AFFINE || a->epi.mode == MDS_EPI_BN_SILU) && a->epi.scale && a->epi.shift,
               "dw_fwd (expand): needs an output transform");
+  if (a->se.gate) SE_TAIL_REQUIRE(a, "dw_fwd (expand)");
   MDS_REQUIRE(!a->pool || a->pool_inv > 0.f, "dw_fwd (expand): pool_inv");
   if (a->stride == 1) {
     MDS_REQUIRE(a->pad_t == 1 && a->pad_l == 1 && a->OH == a->IH && a->OW == a->IW, "dw_fwd (expand): stride-1 geometry");

@@ -203,7 +203,8 @@ def _hip_path():
 class Plan:
     """The recorded schedules + buffers for one configuration."""
 
-    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False):
+    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False,
+                 eval_se_fusion=False):
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
                                     # tail plans: ("probs", tta) - the head also writes the TTA-mean of the sigmoids (mds.predict)
@@ -229,6 +230,9 @@ class Plan:
         # MultiDimStacker.eval_fusion: the 2D inverted-residual blocks of an inference plan expand their input inside the
         # depthwise launch (mds_expand_t) - no mid-wide y1 tensor, no expansion pw_fwd
         self.eval_fusion = bool(eval_fusion) and self.eval_epilogues
+        # MultiDimStacker.eval_se_fusion: the pooling depthwise launch of an inference plan also computes the squeeze-excite
+        # gate (mds_se_tail_t) - no se_fc_fwd launch between the depthwise and the gated projection
+        self.eval_se_fusion = bool(eval_se_fusion) and self.eval_epilogues
         self.in_flight = False
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
@@ -287,6 +291,15 @@ class Plan:
         self._split_part.numel = max(self._split_part.numel, S * int(M) * int(N_))
         self._split_ticket.numel = max(self._split_ticket.numel, -(-int(M) // cabi.MDS_PW_SPLIT_TILE_ROWS) * -(-int(N_) // 128) * cabi.MDS_PW_SPLIT_TICKET_STRIDE)
         return dict(split=S, split_part=self._split_part, split_ticket=self._split_ticket)
+
+    def _se_tickets(self, groups):
+        """tickets of a depthwise launch with the squeeze-excite tail (mds_se_tail_t.ticket): like the split-K tickets they reset
+        themselves, so one zero-initialised buffer serves every block of the plan - launches of one stream"""
+        if getattr(self, "_se_ticket", None) is None:
+            self._se_ticket = Lazy("own0", 0, torch.int32)
+            self._lazy.append(self._se_ticket)
+        self._se_ticket.numel = max(self._se_ticket.numel, int(groups))
+        return self._se_ticket
 
     def zero_fwd(self, n):
         l = self.zf_arena.sub(self._zf, n)
@@ -516,18 +529,27 @@ class Plan:
         pooled, hidden, gate = self.zero_fwd64(groups * mid), self.f32(groups * R), self.f32(groups * mid)
         # the depthwise pass stores the activation AND takes its per-image channel means (the squeeze-excite input): no se_pool launch
         fuse_pool = groups == N and os.environ.get("MDS_EVAL_POOL", "1") == "1"
+        se = blk.se
+        w2t = self.pack(se.conv_expand.weight, cabi.MDS_PACK_IO_F32, mid, R, 1)
+        # ... and, with eval_se_fusion, the block that completes an image's means also computes its gate: no se_fc_fwd launch
+        fuse_se = (self.eval_se_fusion and fuse_pool and mid % 4 == 0 and mid <= cabi.MDS_SE_TAIL_CMAX
+                   and R <= cabi.MDS_SE_TAIL_RMAX)
+        extra = {}
+        if expand is not None:
+            extra["expand"] = expand
+        if fuse_se:
+            extra["se"] = dict(_struct="mds_se_tail_t", R=R, w1=P(se.conv_reduce.weight), b1=P(se.conv_reduce.bias), w2t=w2t,
+                               b2=P(se.conv_expand.bias), hidden=hidden, gate=gate, ticket=self._se_tickets(groups))
         self.op(fseg, "dw_fwd", dtype=self.code, N=N, T=T, IH=IH, IW=IW, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt,
                 pad_l=pl, kt=kt, x=a1, w=P(blk.conv_dw.weight), y=a2, pro=dict(mode=0), stats=None, epi=epi(bn2, EPI_BN_SILU),
-                pool=pooled if fuse_pool else None, pool_inv=1.0 / rpg if fuse_pool else 0.0,
-                **({"expand": expand} if expand is not None else {}))
+                pool=pooled if fuse_pool else None, pool_inv=1.0 / rpg if fuse_pool else 0.0, **extra)
         if not fuse_pool:
             self.op(fseg, "se_pool", dtype=self.code, groups=groups, rows_per_group=rpg, C=mid, y=a2, scale=None, shift=None,
                     pooled=pooled, act=None)
-        se = blk.se
-        w2t = self.pack(se.conv_expand.weight, cabi.MDS_PACK_IO_F32, mid, R, 1)
-        self.op(fseg, "se_fc_fwd", groups=groups, C=mid, R=R, pooled=pooled, w1=P(se.conv_reduce.weight),
-                b1=P(se.conv_reduce.bias), w2=P(se.conv_expand.weight), b2=P(se.conv_expand.bias), hidden=hidden, gate=gate,
-                w2t=w2t)
+        if not fuse_se:
+            self.op(fseg, "se_fc_fwd", groups=groups, C=mid, R=R, pooled=pooled, w1=P(se.conv_reduce.weight),
+                    b1=P(se.conv_reduce.bias), w2=P(se.conv_expand.weight), b2=P(se.conv_expand.bias), hidden=hidden, gate=gate,
+                    w2t=w2t)
         xout = self.act(Mout, cout)
         self.op(fseg, "pw_fwd", dtype=self.code, M=Mout, K=mid, N=cout, x=a2,
                 w=self.pack(blk.conv_pwl.weight, cabi.MDS_PACK_OI, cout, mid, 1), y=xout,
@@ -944,11 +966,11 @@ class Plan:
     cut_hook = None     # data parallelism: called as cut_hook(plan, lo, hi) when arena[lo:hi] is final (all its launches issued)
 
     def _failed(self, rc, name):
-        """a launch was refused: split-K tickets reset themselves only when a launch completes - zero them so that the plan's
-        later launches do not start from a stale count - then raise"""
-        tk = getattr(self, "_split_ticket", None)
-        if tk is not None and tk.tensor is not None:
-            tk.tensor.zero_()
+        """a launch was refused: split-K and squeeze-excite tickets reset themselves only when a launch completes - zero them so
+        that the plan's later launches do not start from a stale count - then raise"""
+        for tk in (getattr(self, "_split_ticket", None), getattr(self, "_se_ticket", None)):
+            if tk is not None and tk.tensor is not None:
+                tk.tensor.zero_()
         self.lib.check(rc, name.split("@")[0])
 
     def run(self, seg):

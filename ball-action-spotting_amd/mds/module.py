@@ -395,6 +395,7 @@ class MultiDimStacker(nn.Module):
         # engine state (not part of state_dict)
         self.compute_dtype = "auto"           # "auto": bf16 under autocast, fp32 otherwise | "bf16" | "f32"
         self.eval_fusion = False              # eval + no-grad plans: the 2D blocks' 1x1 expansion runs inside the depthwise launch
+        self.eval_se_fusion = False           # eval + no-grad plans: the pooling depthwise launch also computes the squeeze-excite gate
         self._cache = _PlanCache()
         self._lib: Optional[cabi.Lib] = None  # tests inject the kernel simulator here; product: cabi.load()
         self._mask_override = None            # parity tests: host-supplied DropPath/dropout masks
@@ -463,7 +464,8 @@ class MultiDimStacker(nn.Module):
         enc_grad = any(p.requires_grad for p in self.conv2d_encoder.parameters())
         code = self._code() if code is None else code
         fusion = bool(getattr(self, "eval_fusion", False))     # (a module unpickled from before the attribute existed: off)
-        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion)
+        se_fusion = bool(getattr(self, "eval_se_fusion", False))
+        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion, se_fusion)
         cache = self._cache
         pool = cache.plans.setdefault(key, [])
         cache.plans.move_to_end(key)
@@ -471,7 +473,8 @@ class MultiDimStacker(nn.Module):
             if not plan.in_flight and not plan.stale():
                 return plan
         pool[:] = [p for p in pool if not p.stale()]
-        plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, eval_fusion=fusion)
+        plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, eval_fusion=fusion,
+                    eval_se_fusion=se_fusion)
         pool.append(plan)
         cache.evict(key)
         return plan

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 133
+#define MDS_VERSION 134
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -314,6 +314,29 @@ typedef struct {
   const float* shift;   /* [C] */
 } mds_expand_t;
 
+/* ---- squeeze-excite tail of the pooling depthwise forward (inference plans; mds_dw_fwd_args.se): the launch that
+ * completes `pool` also turns it into the gate, gate[n] = sigmoid(W2 silu(W1 pool[n] + b1) + b2) - no mds_se_fc_fwd
+ * launch between the depthwise and the gated projection.  Every block, after its pool atomics are acknowledged at
+ * device scope, adds the number of strips (tiles) it flushed for image n to ticket[n]; the block whose add completes
+ * the image's count has, by that order, every partial of pool[n] behind it: it re-reads the row with device-scope
+ * loads and evaluates the two products in fp32, each output in the operation order of mds_se_fc_fwd (the two paths
+ * agree to the last bit or two), then zeroes the ticket for the next launch.  Needs pool != NULL, an output transform,
+ * w2t, 16-byte aligned pool / w1 / w2t / b2 / gate, C % 4 == 0, C <= MDS_SE_TAIL_CMAX, R <= MDS_SE_TAIL_RMAX; anything else is
+ * refused on the host.  A refused or failed launch may leave counts behind: the caller zeroes `ticket` after one.
+ * gate == NULL: off, the launch is the one without this struct, bit for bit.                                       */
+#define MDS_SE_TAIL_CMAX 1280   /* a lane of the tail keeps its five 16-byte chunks of the pooled row in registers */
+#define MDS_SE_TAIL_RMAX 64
+typedef struct {
+  int R;                /* reduced width */
+  const float* w1;      /* [R][C]  conv_reduce */
+  const float* b1;      /* [R] */
+  const float* w2t;     /* [R][C]  MDS_PACK_IO_F32 copy of conv_expand (required here, not optional) */
+  const float* b2;      /* [C] */
+  float* hidden;        /* [groups][R] pre-activation, as mds_se_fc_fwd writes it */
+  float* gate;          /* [groups][C] */
+  int* ticket;          /* [groups], zero before the first launch, self-resetting */
+} mds_se_tail_t;
+
 /* ---- K5/K6: depthwise 3x3 (2D, stride 1 or TF-SAME stride 2) and 3x3x3 (3D, pad 1).
  * Input is the raw output of the preceding 1x1 conv read through a BN+SiLU prologue.
  * replaces timm InvertedResidual.conv_dw and multidim_stacker.py:110-113.
@@ -336,6 +359,7 @@ typedef struct {
   double* pool;        /* optional fp64 [N][C], caller-zeroed */
   float pool_inv;      /* 1 / (T*OH*OW) */
   mds_expand_t expand; /* optional expansion prologue (expand.x != NULL): the depthwise input is computed in the launch */
+  mds_se_tail_t se;    /* optional squeeze-excite tail (se.gate != NULL): the launch also writes the gate of `pool` */
 } mds_dw_fwd_args;
 int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream);
 

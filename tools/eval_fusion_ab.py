@@ -1,14 +1,16 @@
-"""A/B of MultiDimStacker.eval_fusion (the 2D blocks' 1x1 expansion inside the depthwise launch) in ONE process: both settings
-alternate over the same seeded raw 720 x 1280 frames.
+"""A/B of the two opt-in inference fusions in ONE process: MultiDimStacker.eval_fusion ("A": the 2D blocks' 1x1 expansion inside
+the depthwise launch) and MultiDimStacker.eval_se_fusion ("SE": the squeeze-excite gate computed by the pooling depthwise launch).
+The four settings off / A / SE / A+SE alternate over the same seeded raw 720 x 1280 frames.
 
-  python tools/eval_fusion_ab.py [--frames K] [--rounds R]      the table (profiles/r07_eval_fusion_ab.txt)
-  python tools/eval_fusion_ab.py --trace fused|unfused          only predict() fp32 frame by frame with one setting (a child
-                                                                 for rocprofv3 --kernel-trace --stats)
+  python tools/eval_fusion_ab.py [--frames K] [--rounds R]      the table (profiles/r08_eval_se_fusion_ab.txt)
+  python tools/eval_fusion_ab.py --trace off|A|SE|A+SE          only predict() fp32 frame by frame with one setting (a child
+                                                                 for rocprofv3 --kernel-trace --stats; fused / unfused = A / off)
 
-Reports frames/s (median of R alternating rounds) of predict() fp32 frame by frame with TTA off / on, predict_stream 8 x 3, and
-predict() bf16; launches per 2D-encoder pass; the largest difference between the fused and the unfused predictions of the same
-frames; and, per inverted-residual block, the event-timed fused depthwise launch against the expansion pw_fwd + dw_fwd pair it
-replaces (a HIP event pair around every launch of one encoder pass: launches serialised, small ones inflated alike)."""
+Reports frames/s (median of R alternating rounds, and the min - max of the off rounds: the run-to-run spread a ratio has to beat)
+of predict() fp32 frame by frame with TTA off / on, predict_stream 8 x 3, and predict() bf16; launches per 2D-encoder pass; the
+largest difference between each setting's predictions and the off predictions of the same frames; and, per inverted-residual
+block, the event-timed fused depthwise launch of A against the expansion pw_fwd + dw_fwd pair it replaces (a HIP event pair around
+every launch of one encoder pass: launches serialised, small ones inflated alike)."""
 import argparse
 import os
 import statistics
@@ -38,9 +40,13 @@ def make_model():
     return m.eval()
 
 
-def run(m, pool, fusion, K, tta=False, cdt=None, chunk=1, lanes=0):
+SETTINGS = {"off": (False, False), "A": (True, False), "SE": (False, True), "A+SE": (True, True)}      # (eval_fusion, eval_se_fusion)
+
+
+def run(m, pool, setting, K, tta=False, cdt=None, chunk=1, lanes=0):
     """frames/s of K frames after the window is full and the graphs are captured; the predictions of the timed frames"""
-    sp = StreamPredictor(m, frame_size=(1280, 736), tta=tta, compute_dtype=cdt, eval_fusion=fusion)
+    sp = StreamPredictor(m, frame_size=(1280, 736), tta=tta, compute_dtype=cdt, eval_fusion=SETTINGS[setting][0],
+                         eval_se_fusion=SETTINGS[setting][1])
     outs = []
 
     def feed(first, n, keep):
@@ -104,29 +110,33 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--trace", choices=["fused", "unfused"])
+    ap.add_argument("--trace", choices=list(SETTINGS) + ["fused", "unfused"])
     a = ap.parse_args()
     m = make_model()
     pool = torch.randint(0, 256, (64, 720, 1280), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(99))
     if a.trace:
-        fps, _, n = run(m, pool, a.trace == "fused", a.frames)
-        print(f"{a.trace}: predict() fp32 frame by frame {fps:.1f} frames/s, {n} launches per 2D-encoder pass")
+        setting = {"fused": "A", "unfused": "off"}.get(a.trace, a.trace)
+        fps, _, n = run(m, pool, setting, a.frames)
+        print(f"{setting}: predict() fp32 frame by frame {fps:.1f} frames/s, {n} launches per 2D-encoder pass")
         return
     cases = [("predict() fp32, TTA off", dict()), ("predict() fp32, TTA on", dict(tta=True)),
              ("predict_stream fp32, chunk 8 x 3 lanes", dict(chunk=8, lanes=3)), ("predict() bf16, TTA off", dict(cdt="bf16"))]
-    print(f"# eval_fusion A/B: {a.frames} timed frames per run, {a.rounds} alternating rounds (median), device {torch.cuda.get_device_name(0)}")
-    print(f"{'case':40s} {'unfused f/s':>12s} {'fused f/s':>10s} {'ratio':>6s} {'launches 2D pass':>17s} {'max |diff|':>10s}")
+    print(f"# eval_fusion x eval_se_fusion A/B: {a.frames} timed frames per run, {a.rounds} alternating rounds (median), "
+          f"device {torch.cuda.get_device_name(0)}")
+    print(f"{'case':40s} {'setting':>7s} {'frames/s':>9s} {'ratio':>6s} {'rounds min - max':>17s} {'launches 2D pass':>17s} {'max |diff|':>10s}")
     for label, kw in cases:
-        res = {False: [], True: []}
+        res = {k: [] for k in SETTINGS}
         outs, nl = {}, {}
         for _ in range(a.rounds):
-            for fusion in (False, True):
-                fps, out, n = run(m, pool, fusion, a.frames, **kw)
-                res[fusion].append(fps)
-                outs[fusion], nl[fusion] = out, n
-        u, f = statistics.median(res[False]), statistics.median(res[True])
-        diff = (outs[True] - outs[False]).abs().max().item()
-        print(f"{label:40s} {u:12.1f} {f:10.1f} {f / u:6.3f} {nl[False]:>8d} -> {nl[True]:<6d} {diff:10.2e}")
+            for k in SETTINGS:
+                fps, out, n = run(m, pool, k, a.frames, **kw)
+                res[k].append(fps)
+                outs[k], nl[k] = out, n
+        u = statistics.median(res["off"])
+        for k in SETTINGS:
+            f = statistics.median(res[k])
+            diff = (outs[k] - outs["off"]).abs().max().item()
+            print(f"{label if k == 'off' else '':40s} {k:>7s} {f:9.1f} {f / u:6.3f} {min(res[k]):8.1f} - {max(res[k]):<6.1f} {nl[k]:>17d} {diff:10.2e}")
     print()
     print("# per inverted-residual block, fp32, 1 x 736 x 1280 (event-timed launches, median of 5 passes)")
     print(f"{'cin->mid':>10s} {'input':>9s} {'s':>2s} {'pw_fwd us':>10s} {'dw_fwd us':>10s} {'pair us':>8s} {'fused us':>9s} {'ratio':>6s}")
