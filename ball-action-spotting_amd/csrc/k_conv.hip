@@ -479,6 +479,7 @@ __global__ __launch_bounds__(256, (CvqOcc<T, MF, NFR>::v)) void conv_fwd_q_kerne
 }
 
 int c3_try(const mds_conv_fwd_args* a, mds_stream_t stream);   // k_c3.hip: 1 = launched there
+int conv_fwd_project(const mds_conv_fwd_args* a, mds_stream_t stream);   // k_c3p.hip: the launch with a projection tail (mds_project_t)
 
 static int tap_extent(const int* d, int n, int* dmin) {
   int lo = d[0], hi = d[0];
@@ -497,6 +498,7 @@ extern "C" int mds_conv_fwd(const mds_conv_fwd_args* a, mds_stream_t stream) {
   MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || (a->pro.scale && a->pro.shift), "conv_fwd: prologue needs scale/shift");
   MDS_REQUIRE(a->oy0 + (a->A - 1) * a->os < a->OH && a->ox0 + (a->B - 1) * a->os < a->OW, "conv_fwd: sub-grid exceeds output");
   MDS_REQUIRE(a->epi.mode == MDS_EPI_NONE || (a->epi.scale && a->epi.shift && !a->stats), "conv_fwd: an output transform needs scale/shift and excludes statistics");
+  if (a->project.w) return conv_fwd_project(a, stream);           // 3x3 + 1x1 projection in one launch, or an error: never two launches here
   if (c3_try(a, stream)) return mds_check_launch("conv_fwd");    // bf16 layers whose filter slice fits the consumers' registers (k_c3.hip)
   MDS_REQUIRE(a->post.mode == MDS_POST_NONE, "conv_fwd: post statistics only where mds_conv_dgrad_post_ok() says so");
   int dymin, dxmin;

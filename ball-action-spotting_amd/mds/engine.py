@@ -204,7 +204,7 @@ class Plan:
     """The recorded schedules + buffers for one configuration."""
 
     def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False,
-                 eval_se_fusion=False):
+                 eval_se_fusion=False, eval_er_fusion=False):
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
                                     # tail plans: ("probs", tta) - the head also writes the TTA-mean of the sigmoids (mds.predict)
@@ -233,6 +233,9 @@ class Plan:
         # MultiDimStacker.eval_se_fusion: the pooling depthwise launch of an inference plan also computes the squeeze-excite
         # gate (mds_se_tail_t) - no se_fc_fwd launch between the depthwise and the gated projection
         self.eval_se_fusion = bool(eval_se_fusion) and self.eval_epilogues
+        # MultiDimStacker.eval_er_fusion: the edge-residual blocks of an inference plan run their 3x3 expansion and their 1x1
+        # projection in one launch (mds_project_t) - no mid-wide ya tensor, no projection pw_fwd
+        self.eval_er_fusion = bool(eval_er_fusion) and self.eval_epilogues
         self.in_flight = False
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
@@ -756,6 +759,24 @@ class Plan:
     def _er_block(self, recs, blk, xin, xin_bn, N, IH, IW, fr):
         cin, mid, cout = blk.cin, blk.mid, blk.cout
         pro_in = xin_bn.pro() if xin_bn is not None else None
+        if (self.eval_er_fusion and pro_in is None and cin % 8 == 0 and mid % 16 == 0 and cout % 16 == 0
+                and cin <= cabi.MDS_PROJECT_CIN_MAX and mid <= cabi.MDS_PROJECT_MID_MAX and cout <= cabi.MDS_PROJECT_COUT_MAX):
+            # the projection runs inside the 3x3 launch: ya = silu(bn1(conv_exp(xin))) lives in registers only (k_c3p.hip)
+            OH, OW, pt, pl = geo.conv_geometry(IH, IW, blk.stride)
+            M = N * OH * OW
+            bn1, bn2 = BNL(self, blk.bn1, mid, M), BNL(self, blk.bn2, cout, M)
+            bn1.finalize(self, "f2d")         # -> the plan's eval-BatchNorm table
+            bn2.finalize(self, "f2d")
+            dy, dx, wi = geo.taps_fwd(pt, pl)
+            xout = self.act(M, cout)
+            self.op("f2d", "conv_fwd", dtype=self.code, N=N, IH=IH, IW=IW, Cin=cin, OH=OH, OW=OW, Cout=mid, A=OH, B=OW,
+                    oy0=0, ox0=0, os=1, **{"is": blk.stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=xin,
+                    w=self.pack(blk.conv_exp.weight, cabi.MDS_PACK_OI, mid, cin, 9), y=xout, pro=dict(mode=0),
+                    residual=xin if blk.has_skip else None, stats=None,
+                    epi=dict(_struct="mds_epi_t", mode=EPI_BN_SILU, scale=bn1.scale, shift=bn1.shift),
+                    project=dict(_struct="mds_project_t", w=self.pack(blk.conv_pwl.weight, cabi.MDS_PACK_OI, cout, mid, 1), cout=cout,
+                                 scale=bn2.scale, shift=bn2.shift))
+            return xout, OH, OW       # (inference plans have no backward closures)
         ya, bn1, OH, OW, pads = self._conv("f2d", xin, pro_in, N, IH, IW, cin, mid, blk.stride, blk.conv_exp.weight, blk.bn1)
         M = N * OH * OW
         bn2 = BNL(self, blk.bn2, cout, M)

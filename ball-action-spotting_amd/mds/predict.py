@@ -52,12 +52,13 @@ class StreamPredictor:
 
     def __init__(self, nn_module, frame_size=(1280, 736), frame_stack_size: int = 15, frame_stack_step: int = 2,
                  tta: bool = False, use_graphs: bool = True, compute_dtype: str = None, eval_fusion: bool = None,
-                 eval_se_fusion: bool = None):
+                 eval_se_fusion: bool = None, eval_er_fusion: bool = None):
         self.m = nn_module
         self.m.eval()
         self.compute_dtype = compute_dtype               # None: the module's own rule (fp32 outside autocast, like the reference) | "bf16"
         self.eval_fusion = eval_fusion                   # None: the module's own MultiDimStacker.eval_fusion | True / False
         self.eval_se_fusion = eval_se_fusion             # None: the module's own MultiDimStacker.eval_se_fusion | True / False
+        self.eval_er_fusion = eval_er_fusion             # None: the module's own MultiDimStacker.eval_er_fusion | True / False
         self.W, self.H = frame_size                      # PadNormalizeFramesProcessor(size=(width, height))
         self.tta = tta
         self.ss = nn_module.stack_size
@@ -168,12 +169,15 @@ class StreamPredictor:
         m, b = self.m, (2 if self.tta else 1)
         saved, saved_fusion = m.compute_dtype, getattr(m, "eval_fusion", False)
         saved_se = getattr(m, "eval_se_fusion", False)
+        saved_er = getattr(m, "eval_er_fusion", False)
         if self.compute_dtype is not None:
             m.compute_dtype = self.compute_dtype
         if self.eval_fusion is not None:
             m.eval_fusion = bool(self.eval_fusion)
         if self.eval_se_fusion is not None:
             m.eval_se_fusion = bool(self.eval_se_fusion)
+        if self.eval_er_fusion is not None:
+            m.eval_er_fusion = bool(self.eval_er_fusion)
         try:
             with torch.no_grad():
                 probe = self.frames[0]
@@ -191,7 +195,7 @@ class StreamPredictor:
                     c["w"]["tail", len(c["ptail"])] = pt.weight_tensors()
                     c["ptail"].append(pt)
         finally:
-            m.compute_dtype, m.eval_fusion, m.eval_se_fusion = saved, saved_fusion, saved_se
+            m.compute_dtype, m.eval_fusion, m.eval_se_fusion, m.eval_er_fusion = saved, saved_fusion, saved_se, saved_er
         p2d = c["p2d"][0]
         f = p2d.h * p2d.w * m.num_3d_features
         if self.store is None:

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 134
+#define MDS_VERSION 135
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -208,6 +208,27 @@ typedef struct {
 } mds_pw_wgrad_args;
 int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream);
 
+/* ---- projection tail of the dense 3x3 forward (inference plans; mds_conv_fwd_args.project): the 1x1 projection that
+ * follows the 3x3 expansion of an edge-residual block runs in the same launch (k_c3p.hip).  Per output pixel
+ *   y[c] = (sum_m act(conv3x3(x)[m] * epi.scale[m] + epi.shift[m]) * w[c][m]) * scale[c] + shift[c] (+ residual[c]),
+ * y and residual are then [N][OH][OW][cout]; the Cout-wide activated intermediate never exists in device memory: a block
+ * owns a tile of output pixels, walks Cout 32 channels at a time, and the activated accumulators of a chunk ARE (lane for
+ * lane) the B fragments of the second product.  fp32: both products are split-bf16 (three bf16 MFMAs per fragment pair,
+ * fp32 accumulation; -DMDS_EVAL_X3=0: the exact fp32 MFMA); bf16: the activated chunk is rounded to bf16 once, one bf16
+ * MFMA per product.  Zero padding is on x.  Needs epi.mode MDS_EPI_BN_SILU / MDS_EPI_AFFINE, pro.mode == MDS_PRO_NONE,
+ * no stats, no post, no tap groups, os == 1, is 1 or 2, Cin % 8 == 0, Cout % 16 == 0, cout % 16 == 0 and the widths
+ * below; anything else is MDS_ERR_BAD_ARG (never two launches inside the library).  w == NULL: off, the launch is the one
+ * without this struct, bit for bit.                                                                                      */
+#define MDS_PROJECT_CIN_MAX 48     /* the input patch of a tile (all Cin channels) + a 32-channel filter slab share the LDS */
+#define MDS_PROJECT_MID_MAX 256    /* Cout of the 3x3: its output transform is tabled in LDS */
+#define MDS_PROJECT_COUT_MAX 48    /* a wave keeps [its pixels][cout] fp32 accumulators in registers across all chunks */
+typedef struct {
+  const void* w;        /* [cout][Cout] projection filter (MDS_PACK_OI, taps = 1), storage dtype; NULL: off */
+  int cout;             /* projected width */
+  const float* scale;   /* [cout] BatchNorm after the projection (eval table) */
+  const float* shift;   /* [cout] */
+} mds_project_t;
+
 /* ---- K2/K3: dense 3x3 convolution as an MFMA implicit GEMM over a tap list.
  * For output sub-grid point (a,b), a<A, b<B of image n:
  *   y[n][oy0 + a*os][ox0 + b*os][:] = sum_t pro(x)[n][a*is + dy[t]][b*is + dx[t]][:] * w[:][wi[t]][:]
@@ -241,6 +262,7 @@ typedef struct {
   mds_epi_t epi;        /* eval-mode output transform (no statistics with it; applied before `residual` is added) */
   mds_poststat_t post;  /* data-gradient use: the BatchNorm-backward sums of the layer BELOW in the epilogue (PLAIN / MASK with one mask value per
                            image); only launches for which mds_conv_dgrad_post_ok() says 1 may ask for it */
+  mds_project_t project; /* optional 1x1 projection tail (project.w != NULL): y = bn(act(bn(conv3x3(x))) * w^T) (+ residual) in one launch */
 } mds_conv_fwd_args;
 int mds_conv_fwd(const mds_conv_fwd_args* a, mds_stream_t stream);
 /* 1: the bf16 data gradient of a 3x3 layer (forward shape N x IH x IW x Cin -> Cout, stride 1 / 2) takes a kernel that implements `post` */
