@@ -1416,6 +1416,7 @@ struct C3WArgs {
   int nbands, nseg, rps, items;
   int RA, NR;
   const float* pro_scale; const float* pro_shift;      // c3wp_kernel: the input is read through BatchNorm + SiLU
+  float* part; long pstride;      // deterministic way out (mds_partial_t): block b stores its sums to part + b * pstride instead of adding them to dw
 };
 
 template <int NC> MDS_DEV int c3w_rot(int c, int p) {      // where 32-byte chunk c of pixel p sits inside the pixel: 8 consecutive pixels' chunk c tile all 64 banks
@@ -1617,10 +1618,10 @@ __global__ __launch_bounds__(64 * (NCW + NPW)) void c3w_kernel(C3WArgs g) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) fl[(4 * q + r) * SLAB + (16 * c + i) * 9 + g.tapw[t]] = acc[t][c][f][r];
         wave_lds_sync();
-        float* const dst = g.dw + (long)(c0 + 16 * (wave * COW + f)) * SLAB;
+        float* const dst = (g.part ? g.part + (long)blockIdx.x * g.pstride : g.dw) + (long)(c0 + 16 * (wave * COW + f)) * SLAB;      // g.part: this block's slot
         // (every block adds to the same 9 CIN COP addresses: each starts somewhere else)
         const int e0 = (int)((blockIdx.x * 37u) % (16 * SLAB / 64)) * 64;
-        if (!(C3_ABL & 256)) for (int e = lane; e < 16 * SLAB; e += 64) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; atomicAdd(dst + ee, fl[ee]); }
+        if (!(C3_ABL & 256)) for (int e = lane; e < 16 * SLAB; e += 64) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; wg_out(dst + ee, fl[ee], g.part != nullptr); }
         else if (fl[lane] == 12345.678f) dst[lane] = 1.f;
       }
     }
@@ -1872,7 +1873,9 @@ __global__ __launch_bounds__(64 * (4 + NPW + NTW)) void c3wp_kernel(C3WArgs g) {
   wait_lgkm0();
   raw_barrier();
   const int e0 = (int)((blockIdx.x * 37u) % (16 * SLAB / 256)) * 256;
-  for (int e = tid; e < 16 * SLAB; e += 256) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; atomicAdd(g.dw + ee, fl[ee]); }
+  // (the LDS sums above have exactly two terms on a zeroed cell - the two k-step waves of an input fragment: a + b == b + a, their order is free)
+  float* const dst = g.part ? g.part + (long)blockIdx.x * g.pstride : g.dw;
+  for (int e = tid; e < 16 * SLAB; e += 256) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; wg_out(dst + ee, fl[ee], g.part != nullptr); }
 }
 
 // The same for a STRIDE-2 layer (TF-SAME, even extents: blocks.2.0, 32 -> 128): dw[co][ci][ky][kx] += sum dy[r][x][co] in[2 r + ky][2 x + kx][ci].
@@ -2057,9 +2060,9 @@ __global__ __launch_bounds__(64 * (8 + NPW)) void c3w2_kernel(C3WArgs g) {      
 #pragma unroll
           for (int r = 0; r < 4; ++r) fl[(4 * q + r) * SLAB + (16 * c + i) * 9 + g.tapw[t]] = acc[t][c][r];
       wave_lds_sync();
-      float* const dst = g.dw + (long)(c0 + 16 * wave) * SLAB;
+      float* const dst = (g.part ? g.part + (long)blockIdx.x * g.pstride : g.dw) + (long)(c0 + 16 * wave) * SLAB;
       const int e0 = (int)((blockIdx.x * 37u) % (16 * SLAB / 64)) * 64;
-      for (int e = lane; e < 16 * SLAB; e += 64) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; atomicAdd(dst + ee, fl[ee]); }
+      for (int e = lane; e < 16 * SLAB; e += 64) { const int ee = e + e0 < 16 * SLAB ? e + e0 : e + e0 - 16 * SLAB; wg_out(dst + ee, fl[ee], g.part != nullptr); }
     }
     if (rd == 0) { wait_lgkm0(); raw_barrier(); }
   }
@@ -2131,19 +2134,25 @@ static C3WArgs c3w_args(const mds_conv_wgrad_args* a, const int (&tapw)[9], int 
   C3WArgs g = {};
   g.x = (const bf16_t*)a->x; g.dy = (const bf16_t*)a->dyt; g.dw = a->dw; g.pro_scale = a->pro.scale; g.pro_shift = a->pro.shift;
   g.N = a->N; g.H = a->IH; g.W = a->IW; g.Ctot = a->Cout; g.wtaps = a->wtaps; g.RA = RA; g.NR = NR; for (int t = 0; t < 9; ++t) g.tapw[t] = tapw[t];
+  g.part = a->partial.buf; g.pstride = wg_floats((long)a->Cout * a->Cin * a->wtaps, 1);      // deterministic way out: slot = blockIdx.x
   return g;
 }
 
 template <class A> using C3Launch = void (*)(const A*, const int (&)[9], mds_stream_t);
-template <class A> struct C3Route { C3Launch<A> launch; int tapw[9]; };      // launch nullptr: not a shape of these kernels
+template <class A> struct C3Route { C3Launch<A> launch; int tapw[9]; int (*gridx)(const A*); };      // launch nullptr: not a shape of these kernels; gridx (weight gradients): the launch's grid.x
 template <class A> static int c3_go(const C3Route<A>& r, const A* a, mds_stream_t s) { if (r.launch) r.launch(a, r.tapw, s); return r.launch != nullptr; }
+// grid.x of the three weight-gradient launches (= the slots of the deterministic way out): the launchers and c3w_slots come here
+static int c3wp_grid(const mds_conv_wgrad_args* a, C3WArgs& g) { return c3_split(g, a->IH, cdiv(a->IW, 64), c3_blocks(1, false), 1, 4); }
+template <int COP> static int c3w_grid(const mds_conv_wgrad_args* a, C3WArgs& g) { return c3_split(g, a->IH, cdiv(a->IW, 32), c3_blocks(a->Cout / COP, false), 1, 4); }
+static int c3w2_grid(const mds_conv_wgrad_args* a, C3WArgs& g) { return c3_split(g, a->OH, cdiv(a->OW, 32), c3_blocks(1, false), 1, 3); }
+template <int (*F)(const mds_conv_wgrad_args*, C3WArgs&)> static int c3w_gridx(const mds_conv_wgrad_args* a) { C3WArgs g = {}; g.N = a->N; return F(a, g); }
 template <int NPW, int NTW>
 static void c3wp_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_stream_t stream) {
   constexpr int PPX = 4, PPY = 2, WB = 64, XS = (WB + 2) * PPX, XSP = (XS + 63) / 64 * 64, RS = XSP + WB * PPY, PIECES = RS / 64, ROWB = RS * 16;
   // the ring is the whole LDS (a batch dips it by three rows): the batch being consumed + the one being transformed + the entry above / below
   typedef C3Ring<ROWB, PIECES, NPW, 100 * 1024, 3, 2 * C3WP_BATCH + 2, 158 * 1024> R;
   C3WArgs g = c3w_args(a, tapw, R::RA, R::NR);
-  const int grid = c3_split(g, a->IH, cdiv(a->IW, WB), c3_blocks(1, false), 1, 4);
+  const int grid = c3wp_grid(a, g);
   const size_t smem = (size_t)R::NR * ROWB > (size_t)16 * 32 * 9 * 4 ? (size_t)R::NR * ROWB : (size_t)16 * 32 * 9 * 4;
   MDS_LAUNCH((c3wp_kernel<NPW, NTW>), dim3(grid), dim3(64 * (4 + NPW + NTW)), smem, stream, g);
 }
@@ -2152,7 +2161,8 @@ static void c3w_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_s
   constexpr int COP = 16 * COW * NCW, PPX = CIN / 8, PPY = COP / 8, WB = 32, XS = (WB + 2) * PPX, XSP = (XS + 63) / 64 * 64, RS = XSP + WB * PPY, PIECES = RS / 64, ROWB = RS * 16;
   typedef C3Ring<ROWB, PIECES, NPW, 80 * 1024, 3, 6, 158 * 1024> R;      // the consumers read back to entry k0 - 2 of the batch (+ one of slack)
   C3WArgs g = c3w_args(a, tapw, R::RA, R::NR);
-  const int passes = a->Cout / COP, grid = c3_split(g, a->IH, cdiv(a->IW, WB), c3_blocks(passes, false), 1, 4);
+  static_assert(WB == 32, "c3w_grid's band width");
+  const int passes = a->Cout / COP, grid = c3w_grid<COP>(a, g);
   const size_t flush = (size_t)4 * 16 * CIN * 9 * 4, smem = (size_t)R::NR * ROWB > flush ? (size_t)R::NR * ROWB : flush;
   MDS_LAUNCH((c3w_kernel<CIN, COW, NCW, NPW>), dim3(grid, passes), dim3(64 * (NCW + NPW)), smem, stream, g);
 }
@@ -2161,7 +2171,8 @@ static void c3w2_launch(const mds_conv_wgrad_args* a, const int (&tapw)[9], mds_
   constexpr int WB = 32, XSP = ((2 * WB + 1) * 4 + 63) / 64 * 64, RS = 2 * XSP + WB * 16, PIECES = RS / 64, ROWB = RS * 16;
   typedef C3Ring<ROWB, PIECES, NPW, 5 * ROWB, 2, 3, 158 * 1024> R;      // five entries in flight
   C3WArgs g = c3w_args(a, tapw, R::RA, R::NR);
-  const int grid = c3_split(g, a->OH, cdiv(a->OW, WB), c3_blocks(1, false), 1, 3);
+  static_assert(WB == 32, "c3w2_grid's band width");
+  const int grid = c3w2_grid(a, g);
   MDS_LAUNCH((c3w2_kernel<NPW>), dim3(grid, 1), dim3(64 * (8 + NPW)), (size_t)R::NR * ROWB, stream, g);
 }
 // mds_conv_wgrad's large bf16 launches: blocks.1.1 / 2.1, 2.0 (stride 2, TF-SAME pads 0 / 1, even extents), 0.0 (behind the stem's BN + SiLU)
@@ -2173,17 +2184,27 @@ static C3Route<mds_conv_wgrad_args> c3w_route(const mds_conv_wgrad_args* a) {
     if (a->Cin != 32 || a->Cout != 128 || a->pro.mode != MDS_PRO_NONE) return r;
     if (a->IH % 2 || a->IW % 2 || a->OH != a->IH / 2 || a->OW != a->IW / 2) return r;
     if ((long)a->IH * a->IW * a->Cin >= (1L << 30) || (long)a->OH * a->OW * a->Cout >= (1L << 30)) return r;
-    if (c3_tapmap(r.tapw, a->dy, a->dx, a->wi, 9, C3_S2) && ((long)a->N * a->OH * a->OW >= 16384 || knob == 2)) r.launch = c3w2_launch<3>;
+    if (c3_tapmap(r.tapw, a->dy, a->dx, a->wi, 9, C3_S2) && ((long)a->N * a->OH * a->OW >= 16384 || knob == 2)) { r.launch = c3w2_launch<3>; r.gridx = c3w_gridx<c3w2_grid>; }
     return r;
   }
   if (a->is != 1 || (a->pro.mode != MDS_PRO_NONE && !pro) || a->OH != a->IH || a->OW != a->IW) return r;
   if (pro && !(a->Cin == 32 && a->Cout == 16 && a->pro.scale && a->pro.shift)) return r;
   if ((long)a->IH * a->IW * a->Cout >= (1L << 30)) return r;
   if (!c3_tapmap(r.tapw, a->dy, a->dx, a->wi, 9, C3_S1) || ((long)a->N * a->IH * a->IW < 16384 && knob != 2)) return r;
-  if (pro) r.launch = c3wp_launch<3, 8>;
-  else if (a->Cin == 32 && a->Cout == 128) r.launch = c3w_launch<32, 1, 8, 3>;      // blocks.1.1: eight consumer waves of one 16-channel fragment each
-  else if (a->Cin == 48 && a->Cout == 192) r.launch = c3w_launch<48, 1, 6, 2>;      // blocks.2.1: two passes of 96 channels, six consumer waves
+  if (pro) { r.launch = c3wp_launch<3, 8>; r.gridx = c3w_gridx<c3wp_grid>; }
+  else if (a->Cin == 32 && a->Cout == 128) { r.launch = c3w_launch<32, 1, 8, 3>; r.gridx = c3w_gridx<c3w_grid<128>>; }      // blocks.1.1: eight consumer waves of one 16-channel fragment each
+  else if (a->Cin == 48 && a->Cout == 192) { r.launch = c3w_launch<48, 1, 6, 2>; r.gridx = c3w_gridx<c3w_grid<96>>; }      // blocks.2.1: two passes of 96 channels, six consumer waves
   return r;
+}
+// grid.x of the launch c3w_try would make (0: k_conv.hip's kernel; -1: an experiment build that cannot fill slots).  The route looks at the prologue pointers, never through them:
+// the partial-buffer query may come without buffers
+int c3w_slots(const mds_conv_wgrad_args* a) {
+  static const float dummy = 0;
+  mds_conv_wgrad_args c = *a;
+  if (c.pro.mode != MDS_PRO_NONE) c.pro.scale = c.pro.shift = &dummy;
+  const C3Route<mds_conv_wgrad_args> r = c3w_route(&c);
+  if (r.launch && (C3_ABL & (256 | 512 | 1024))) return -1;      // an ablation build whose weight-gradient kernels skip their sums or stores: no partial buffer
+  return r.launch ? r.gridx(&c) : 0;
 }
 
 int c3w_try(const mds_conv_wgrad_args* a, mds_stream_t stream) { return c3_go(c3w_route(a), a, stream); }      // 1 = launched, 0 = k_conv.hip's kernel

@@ -838,20 +838,52 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(mds_conv_wgrad_args a, 
       }
     }
     __syncthreads();
-    float* dst = a.dw + (long)(co0 + 16 * cf) * slab;
-    for (int e = tid; e < 16 * slab; e += 256) atomicAdd(dst + e, flush[e]);
+    float* dst = wg_base(a.dw, a.partial, (long)Cout * slab, blockIdx.x) + (long)(co0 + 16 * cf) * slab;      // deterministic way out: slot = blockIdx.x
+    const bool det = a.partial.buf != nullptr;
+    for (int e = tid; e < 16 * slab; e += 256) wg_out(dst + e, flush[e], det);
   }
 }
 
 int c3w_try(const mds_conv_wgrad_args* a, mds_stream_t stream);      // k_c3.hip: the large stride-1 bf16 launches, row streaming; 1 = launched
+int c3w_slots(const mds_conv_wgrad_args* a);                        // k_c3.hip: grid.x of that launch (0: not one of its shapes)
+// launch geometry of this file's kernel: the launcher and the partial-buffer query both come here
+struct CwGeo { int tpb, gx, cot; long total; };
+static CwGeo conv_wgrad_geo(const mds_conv_wgrad_args* a) {
+  CwGeo g;
+  const int tiles_a = cdiv(a->OH, CV_TA), tiles_b = cdiv(a->OW, CV_TB);
+  const long total = g.total = (long)a->N * tiles_a * tiles_b;
+  const int cot = g.cot = cdiv(a->Cout, CW_COT);
+  // one block per CU (the accumulators take the register file); every block ends with an atomic per
+  // filter value, so: two rounds of the chip for the big layers, one for the small (measured)
+  long want = (total >= 4096 ? 512 : 256) / cot;   // (re-measured inside the training step: 64 / 128 lose 12 % / 2 %, 256...1024 are flat)
+  if (want < 1) want = 1;
+  int tpb = (int)((total + want - 1) / want);
+  if (tpb < 1) tpb = 1;
+  g.tpb = tpb; g.gx = cdiv(total, tpb);      // every grid.x index flushes all Cout * Cin * wtaps values (over grid.y): gx slots
+  return g;
+}
+#define CONV_WGRAD_DIMS_OK(a) \
+  MDS_REQUIRE(a && a->N > 0 && a->OH > 0 && a->OW > 0, "conv_wgrad: bad dims"); \
+  MDS_REQUIRE(a->Cin % 16 == 0 && a->Cin <= 48 && a->Cout % 16 == 0, "conv_wgrad: needs Cin in {16,32,48}, Cout %% 16 (Cin=%d Cout=%d)", a->Cin, a->Cout); \
+  MDS_REQUIRE(a->ntaps >= 1 && a->ntaps <= MDS_MAX_TAPS && a->is >= 1, "conv_wgrad: taps/stride"); \
+  MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || a->pro.mode == MDS_PRO_AFFINE || a->pro.mode == MDS_PRO_BN_SILU, "conv_wgrad: prologue mode")
+static long conv_wgrad_slots(const mds_conv_wgrad_args* a) { const int s = c3w_slots(a); return s ? s : conv_wgrad_geo(a).gx; }      // (< 0: c3w_slots)
+extern "C" long mds_conv_wgrad_partial_floats(const mds_conv_wgrad_args* a) {
+  CONV_WGRAD_DIMS_OK(a);
+  MDS_REQUIRE(conv_wgrad_slots(a) > 0, "conv_wgrad: this build of k_c3.hip (C3_ABL) leaves slots unwritten: no partial buffer");
+  return wg_floats((long)a->Cout * a->Cin * a->wtaps, conv_wgrad_slots(a));
+}
 extern "C" int mds_conv_wgrad(const mds_conv_wgrad_args* a, mds_stream_t stream) {
-  MDS_REQUIRE(a && a->N > 0 && a->OH > 0 && a->OW > 0, "conv_wgrad: bad dims");
-  MDS_REQUIRE(a->Cin % 16 == 0 && a->Cin <= 48 && a->Cout % 16 == 0, "conv_wgrad: needs Cin in {16,32,48}, Cout %% 16 (Cin=%d Cout=%d)", a->Cin, a->Cout);
-  MDS_REQUIRE(a->ntaps >= 1 && a->ntaps <= MDS_MAX_TAPS && a->is >= 1, "conv_wgrad: taps/stride");
+  CONV_WGRAD_DIMS_OK(a);
   MDS_REQUIRE(a->x && a->dyt && a->dw, "conv_wgrad: null pointer");
-  MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || a->pro.mode == MDS_PRO_AFFINE || a->pro.mode == MDS_PRO_BN_SILU, "conv_wgrad: prologue mode");
   MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || (a->pro.scale && a->pro.shift), "conv_wgrad: prologue needs scale/shift");
-  if (c3w_try(a, stream)) return mds_check_launch("conv_wgrad");
+  const long numel = (long)a->Cout * a->Cin * a->wtaps, slots = conv_wgrad_slots(a);
+  MDS_REQUIRE(!a->partial.buf || slots > 0, "conv_wgrad: this build of k_c3.hip (C3_ABL) leaves slots unwritten: no partial buffer");
+  MDS_PARTIAL_OK(a->partial, wg_floats(numel, slots > 0 ? slots : 0), "conv_wgrad");
+  if (c3w_try(a, stream)) {
+    if (int rc = mds_check_launch("conv_wgrad")) return rc;
+    return wg_finish(a->partial, a->dw, numel, slots, stream);
+  }
   int dymin, dxmin;
   const int eh = tap_extent(a->dy, a->ntaps, &dymin), ew = tap_extent(a->dx, a->ntaps, &dxmin);
   const int TH = (CV_TA - 1) * a->is + eh + 1, TW = (CV_TB - 1) * a->is + ew + 1;
@@ -859,15 +891,9 @@ extern "C" int mds_conv_wgrad(const mds_conv_wgrad_args* a, mds_stream_t stream)
   MDS_REQUIRE(TH * TW * (a->Cin / 8) <= 9 * 256, "conv_wgrad: input patch %dx%dx%d exceeds the staging registers", TH, TW, a->Cin);
   MDS_REQUIRE((long)a->IH * a->IW * a->Cin < 2147483647L && (long)a->OH * a->OW * a->Cout < 2147483647L, "conv_wgrad: one image must stay below 2^31 elements");
   const int xl = cdiv(TH * TW * (a->Cin / 8), 256);
-  const long total = (long)a->N * tiles_a * tiles_b;
-  const int cot = cdiv(a->Cout, CW_COT);
-  // one block per CU (the accumulators take the register file); every block ends with an atomic per
-  // filter value, so: two rounds of the chip for the big layers, one for the small (measured)
-  long want = (total >= 4096 ? 512 : 256) / cot;   // (re-measured inside the training step: 64 / 128 lose 12 % / 2 %, 256...1024 are flat)
-  if (want < 1) want = 1;
-  int tpb = (int)((total + want - 1) / want);
-  if (tpb < 1) tpb = 1;
-  dim3 grid(cdiv(total, tpb), cot), block(256);
+  const CwGeo cg = conv_wgrad_geo(a);
+  const int cot = cg.cot, tpb = cg.tpb;
+  dim3 grid(cg.gx, cot), block(256);
   MDS_REQUIRE(a->ntaps <= 9, "conv_wgrad: at most 9 taps");
   const int cifr = a->Cin >> 4;
   const size_t smem_elems = (size_t)TH * TW * cw_ldx(a->dtype, a->Cin) + 128 * cw_ldy(a->dtype);
@@ -889,5 +915,6 @@ extern "C" int mds_conv_wgrad(const mds_conv_wgrad_args* a, mds_stream_t stream)
 #undef CW_GO5
 #undef CW_GO3
 #undef CW_GO
-  return mds_check_launch("conv_wgrad");
+  if (int rc = mds_check_launch("conv_wgrad")) return rc;
+  return wg_finish(a->partial, a->dw, numel, slots, stream);
 }

@@ -549,7 +549,7 @@ __global__ __launch_bounds__(256, 2) void dw2_bwd_kernel(mds_dw_bwd_args a, DwSt
     float v = 0.f;
 #pragma unroll
     for (int s = 0; s < 8; ++s) v += dwl[s][t][c];
-    if (cbeg + c < C) atomicAdd(a.dw + (long)cbeg * 9 + e, v);
+    if (cbeg + c < C) wg_out(wg_base(a.dw, a.partial, (long)C * 9, bx) + (long)cbeg * 9 + e, v, a.partial.buf != nullptr);      // deterministic way out: slot = strip block
   }
   if (tid < 128) {
     const int kk = tid >> 6, c = tid & 63;
@@ -963,7 +963,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 1 : MDS_DW3B_OCC) void dw3_bw
     float v = 0.f;
 #pragma unroll
     for (int s = 0; s < 8; ++s) v += dwl[s][t][c];
-    if (cbeg + c < C) atomicAdd(a.dw + (long)cbeg * 27 + e, v);
+    if (cbeg + c < C) wg_out(wg_base(a.dw, a.partial, (long)C * 27, bx) + (long)cbeg * 27 + e, v, a.partial.buf != nullptr);      // deterministic way out: slot = strip block
   }
   if (tid < 128) {
     const int kk = tid >> 6, c = tid & 63;
@@ -1211,7 +1211,7 @@ __global__ __launch_bounds__(256, 2) void dw2s_bwd_kernel(mds_dw_bwd_args a, DwS
     float v = 0.f;
 #pragma unroll
     for (int s = 0; s < 8; ++s) v += dwl[s][t][c];
-    if (cbeg + c < C) atomicAdd(a.dw + (long)cbeg * 9 + e, v);
+    if (cbeg + c < C) wg_out(wg_base(a.dw, a.partial, (long)C * 9, bx) + (long)cbeg * 9 + e, v, a.partial.buf != nullptr);      // deterministic way out: slot = strip block
   }
   if (tid < 128) {
     const int kk = tid >> 6, c = tid & 63;
@@ -1544,13 +1544,24 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(mds_dw_bwd_args a, int nchu
     }
   }
   // reductions: same-chunk lanes of the wave by shuffles, then LDS, then coalesced global atomics
+  // (deterministic way out: the four waves add to the LDS cells one after the other - four terms per cell, their order counts -
+  //  and the block stores the cells to its slot)
+  const bool det = a.partial.buf != nullptr;
+  for (int w = 0; w < (det ? 4 : 1); ++w) {
+    if (!det || (tid >> 6) == w) {
 #pragma unroll
-  for (int t = 0; t < NTAP; ++t)
+      for (int t = 0; t < NTAP; ++t)
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float s = sum_same_chunk<NCH>(dwacc[t][j]);
-      if ((tid & 63) < NCH) atomicAdd(&dwl[(ch * V + j) * NTAP + t], s);
+        for (int j = 0; j < V; ++j) {
+          float s = sum_same_chunk<NCH>(dwacc[t][j]);
+          if ((tid & 63) < NCH) {
+            if (det) dwl[(ch * V + j) * NTAP + t] += s;
+            else atomicAdd(&dwl[(ch * V + j) * NTAP + t], s);
+          }
+        }
     }
+    if (det) __syncthreads();
+  }
 #pragma unroll
   for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -1560,7 +1571,7 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(mds_dw_bwd_args a, int nchu
     }
   __syncthreads();
   for (int e = tid; e < NTAP * CC; e += 256) {
-    if (cbeg + e / NTAP < C) atomicAdd(a.dw + (long)cbeg * NTAP + e, dwl[e]);
+    if (cbeg + e / NTAP < C) wg_out(wg_base(a.dw, a.partial, (long)C * NTAP, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * n)) + (long)cbeg * NTAP + e, dwl[e], det);
   }
   if (tid < 2 * CC) {
     const int k = tid / CC, c = tid - k * CC;
@@ -1571,54 +1582,74 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(mds_dw_bwd_args a, int nchu
   }
 }
 
+// launch geometry of mds_dw_bwd: the launcher and the partial-buffer query both come here
+struct DwBwdGeo { int path; DwStrips g; dim3 grid; int nchunks, tpb; long slots; };      // path 0 / 1 / 2: the sliding-window kernels (3x3 stride 1, stride 2, 3x3x3 at T = 5), 3: the tiled one
+static DwBwdGeo dw_bwd_geo(const mds_dw_bwd_args* a) {
+  DwBwdGeo q = {};
+  if (a->kt == 1 && a->stride == 1) { q.path = 0; q.g = dw_strips(a->N * a->T, a->IH, a->IW, a->C, 4, dw2_len(a->N * a->T, a->IH, a->IW, a->C, 4)); }
+  else if (a->kt == 1 && a->stride == 2) { q.path = 1; q.g = dw_strips(a->N * a->T, a->IH, a->IW, a->C, 4, 16, true); }
+  else if (a->kt == 3 && a->T == DW3_T) { q.path = 2; q.g = dw_strips(a->N, a->IH, a->IW, a->C, 1, dw3_len(a->N, a->IH, a->IW, a->C, 16)); }
+  else {
+    q.path = 3;
+    q.nchunks = cdiv(a->C, a->dtype == MDS_BF16 ? DwCfg<bf16_t>::CC : DwCfg<float>::CC);
+    const int tiles_x = cdiv(a->IW, 16);
+    // the per-block fixed cost (tap staging, 36-value wave reductions, atomics) is amortised over a
+    // whole row band in 2D (measured: 342 -> 215 us at 46x80x672); 3D blocks already walk T slices
+    q.tpb = a->kt == 3 ? 2 : (tiles_x < 8 ? tiles_x : 8);
+    q.grid = dim3(cdiv(tiles_x, q.tpb), cdiv(a->IH, 8), a->N * q.nchunks);
+    q.slots = (long)q.grid.x * q.grid.y * a->N;      // every (tile run, row band, image) flushes all C channels over its chunk blocks
+    return q;
+  }
+  q.grid = dw_grid(q.g);
+  q.slots = cdiv(q.g.nstrips, 8 * q.g.spt);          // strip blocks; each flushes all C channels over its chunk blocks
+  return q;
+}
+#define DW_BWD_DIMS_OK(a) \
+  MDS_REQUIRE(a && a->N > 0 && a->T > 0 && a->C % 8 == 0, "dw_bwd: bad dims"); \
+  MDS_REQUIRE(a->kt == 1 || a->kt == 3, "dw_bwd: kt must be 1 or 3"); \
+  MDS_REQUIRE(a->stride == 1 || a->stride == 2, "dw_bwd: stride"); \
+  MDS_REQUIRE(!(a->kt == 3 && a->stride == 2), "dw_bwd: 3x3x3 is stride 1 only"); \
+  MDS_REQUIRE(a->dtype == MDS_F32 || a->dtype == MDS_BF16, "dw_bwd: dtype"); \
+  MDS_REQUIRE((long)a->N * 64 < 65536, "dw_bwd: grid.z")
+extern "C" long mds_dw_bwd_partial_floats(const mds_dw_bwd_args* a) {
+  DW_BWD_DIMS_OK(a);
+  return wg_floats((long)a->C * a->kt * 9, dw_bwd_geo(a).slots);
+}
 extern "C" int mds_dw_bwd(const mds_dw_bwd_args* a, mds_stream_t stream) {
-  MDS_REQUIRE(a && a->N > 0 && a->T > 0 && a->C % 8 == 0, "dw_bwd: bad dims");
-  MDS_REQUIRE(a->kt == 1 || a->kt == 3, "dw_bwd: kt must be 1 or 3");
-  MDS_REQUIRE(a->stride == 1 || a->stride == 2, "dw_bwd: stride");
-  MDS_REQUIRE(!(a->kt == 3 && a->stride == 2), "dw_bwd: 3x3x3 is stride 1 only");
+  DW_BWD_DIMS_OK(a);
   MDS_REQUIRE(a->x && a->dy && a->w && a->g && a->dw && a->stats && a->mean && a->rstd, "dw_bwd: null pointer");
   MDS_REQUIRE(a->pro.mode == MDS_PRO_BN_SILU && a->pro.scale && a->pro.shift, "dw_bwd: needs the BN+SiLU prologue of the forward");
   MDS_REQUIRE(a->stride == 2 ? (a->pad_l == 0 || a->pad_l == 1) : (a->pad_l == 1 && a->pad_t == 1), "dw_bwd: pad=(%d,%d) unsupported for stride %d", a->pad_t, a->pad_l, a->stride);
-  MDS_REQUIRE((long)a->N * 64 < 65536, "dw_bwd: grid.z");
-  if (a->kt == 1 && a->stride == 1) {
+  DwBwdGeo q = dw_bwd_geo(a);
+  const long numel = (long)a->C * a->kt * 9;
+  MDS_PARTIAL_OK(a->partial, wg_floats(numel, q.slots), "dw_bwd");
+  DwStrips& g = q.g;
+  const dim3 grid = q.grid, block(256);
+  if (q.path == 0) {
     MDS_REQUIRE(a->OH == a->IH && a->OW == a->IW, "dw_bwd: stride-1 geometry");
-    DwStrips g = dw_strips(a->N * a->T, a->IH, a->IW, a->C, 4, dw2_len(a->N * a->T, a->IH, a->IW, a->C, 4));
-    dim3 grid = dw_grid(g), block(256);
     MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_bwd_kernel<T, 4>), grid, block, 0, stream, *a, g));
-    return mds_check_launch("dw_bwd");
-  }
-  if (a->kt == 1 && a->stride == 2) {
+  } else if (q.path == 1) {
     MDS_REQUIRE((a->pad_t == 0 || a->pad_t == 1), "dw_bwd: pad_t");
-    DwStrips g = dw_strips(a->N * a->T, a->IH, a->IW, a->C, 4, 16, true);
-    dim3 grid = dw_grid(g), block(256);
     MDS_DISPATCH_DTYPE(a->dtype, T, {
       if (a->pad_t == 0 && a->pad_l == 0) MDS_LAUNCH((dw2s_bwd_kernel<T, 0, 0>), grid, block, 0, stream, *a, g);
       else if (a->pad_t == 0) MDS_LAUNCH((dw2s_bwd_kernel<T, 0, 1>), grid, block, 0, stream, *a, g);
       else if (a->pad_l == 0) MDS_LAUNCH((dw2s_bwd_kernel<T, 1, 0>), grid, block, 0, stream, *a, g);
       else MDS_LAUNCH((dw2s_bwd_kernel<T, 1, 1>), grid, block, 0, stream, *a, g);
     });
-    return mds_check_launch("dw_bwd");
-  }
-  if (a->kt == 3 && a->T == DW3_T) {
-    DwStrips g = dw_strips(a->N, a->IH, a->IW, a->C, 1, dw3_len(a->N, a->IH, a->IW, a->C, 16));
-    dim3 grid = dw_grid(g), block(256);
+  } else if (q.path == 2) {
     MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(dw3_bwd_kernel<T>, grid, block, 0, stream, *a, g));
-    return mds_check_launch("dw_bwd");
+  } else {
+    MDS_DISPATCH_DTYPE(a->dtype, T, {
+      const int CC = DwCfg<T>::CC;
+      const int nchunks = q.nchunks, tpb = q.tpb;
+      const int dnpix = a->stride == 1 ? 10 * 18 : 6 * 10;
+      const size_t smem = (size_t)a->kt * dnpix * CC * sizeof(T) + ((size_t)2 * a->kt * 9 * CC + 4 * CC) * sizeof(float);
+      if (a->kt == 3) MDS_LAUNCH((dw_bwd_kernel<T, 1, 1, 3>), grid, block, smem, stream, *a, nchunks, tpb);
+      else if (a->stride == 1) MDS_LAUNCH((dw_bwd_kernel<T, 1, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
+      else if (a->pad_l == 0) MDS_LAUNCH((dw_bwd_kernel<T, 2, 0, 1>), grid, block, smem, stream, *a, nchunks, tpb);
+      else MDS_LAUNCH((dw_bwd_kernel<T, 2, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
+    });
   }
-  MDS_DISPATCH_DTYPE(a->dtype, T, {
-    const int CC = DwCfg<T>::CC;
-    const int nchunks = cdiv(a->C, CC);
-    const int tiles_x = cdiv(a->IW, 16);
-    // the per-block fixed cost (tap staging, 36-value wave reductions, atomics) is amortised over a
-    // whole row band in 2D (measured: 342 -> 215 us at 46x80x672); 3D blocks already walk T slices
-    int tpb = a->kt == 3 ? 2 : (tiles_x < 8 ? tiles_x : 8);
-    dim3 grid(cdiv(tiles_x, tpb), cdiv(a->IH, 8), a->N * nchunks), block(256);
-    const int dnpix = a->stride == 1 ? 10 * 18 : 6 * 10;
-    const size_t smem = (size_t)a->kt * dnpix * CC * sizeof(T) + ((size_t)2 * a->kt * 9 * CC + 4 * CC) * sizeof(float);
-    if (a->kt == 3) MDS_LAUNCH((dw_bwd_kernel<T, 1, 1, 3>), grid, block, smem, stream, *a, nchunks, tpb);
-    else if (a->stride == 1) MDS_LAUNCH((dw_bwd_kernel<T, 1, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
-    else if (a->pad_l == 0) MDS_LAUNCH((dw_bwd_kernel<T, 2, 0, 1>), grid, block, smem, stream, *a, nchunks, tpb);
-    else MDS_LAUNCH((dw_bwd_kernel<T, 2, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
-  });
-  return mds_check_launch("dw_bwd");
+  if (int rc = mds_check_launch("dw_bwd")) return rc;
+  return wg_finish(a->partial, a->dw, numel, q.slots, stream);
 }

@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void gem_bwd_kernel(mds_gem_bwd_args a) {
   if (threadIdx.x == 0) {
     float s = 0.f;
     for (int i = 0; i < 256; ++i) s += red[i];
-    atomicAdd(a.dp, s);
+    wg_out(wg_base(a.dp, a.partial, 1, blockIdx.x), s, a.partial.buf != nullptr);      // deterministic way out: slot = group
   }
 }
 // row-split backward, second launch: u = coef * c^(p-1) * [a >= eps] with coef recomputed per block from
@@ -542,12 +542,18 @@ __global__ __launch_bounds__(256) void gem_apply_kernel(mds_gem_bwd_args a) {
     if (threadIdx.x == 0) {
       float s = 0.f;
       for (int i = 0; i < 256; ++i) s += red[i];
-      atomicAdd(a.dp, s);
+      wg_out(wg_base(a.dp, a.partial, 1, blockIdx.x), s, a.partial.buf != nullptr);      // deterministic way out: slot = group (its split 0)
     }
   }
 }
+#define GEM_BWD_DIMS_OK(a) MDS_REQUIRE(a && a->groups > 0 && a->rows_per_group > 0 && a->C % 8 == 0 && a->C <= 2048, "gem_bwd: bad dims")
+extern "C" long mds_gem_bwd_partial_floats(const mds_gem_bwd_args* a) {      // one dp term per group, in both forms
+  GEM_BWD_DIMS_OK(a);
+  return wg_floats(1, a->groups);
+}
 extern "C" int mds_gem_bwd(const mds_gem_bwd_args* a, mds_stream_t stream) {
-  MDS_REQUIRE(a && a->groups > 0 && a->rows_per_group > 0 && a->C % 8 == 0 && a->C <= 2048, "gem_bwd: bad dims");
+  GEM_BWD_DIMS_OK(a);
+  MDS_PARTIAL_OK(a->partial, wg_floats(1, a->groups), "gem_bwd");
   if (a->accum) {
     const int sp = gem_splits(a->groups, a->rows_per_group, a->C);
     MDS_DISPATCH_DTYPE(a->dtype, T, {
@@ -555,8 +561,9 @@ extern "C" int mds_gem_bwd(const mds_gem_bwd_args* a, mds_stream_t stream) {
                  a->pro, a->p, a->eps, a->accum);
       MDS_LAUNCH(gem_apply_kernel<T>, dim3(a->groups, sp), dim3(256), 0, stream, *a);
     });
-    return mds_check_launch("gem_bwd");
+  } else {
+    MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(gem_bwd_kernel<T>, dim3(a->groups), dim3(256), 0, stream, *a));
   }
-  MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(gem_bwd_kernel<T>, dim3(a->groups), dim3(256), 0, stream, *a));
-  return mds_check_launch("gem_bwd");
+  if (int rc = mds_check_launch("gem_bwd")) return rc;
+  return wg_finish(a->partial, a->dp, 1, a->groups, stream);
 }

@@ -575,6 +575,8 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(mds_pw_wgrad_args a, i
   const T* x = (const T*)a.x;
   const T* dy = (const T*)a.dy;
   const int kfr = (K - kt0 >= KT) ? KF : ((K - kt0 + 15) >> 4);
+  const bool det = a.partial.buf != nullptr;      // deterministic way out: this row split's slot, plain stores
+  float* const dw = wg_base(a.dw, a.partial, (long)N * K, blockIdx.x);
 
   // when 256 % XCH == 0 a thread keeps the same 8-channel slice for every staged item: its BN
   // scale/shift live in registers for the whole kernel
@@ -691,7 +693,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(mds_pw_wgrad_args a, i
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int n = n0 + 16 * (NF * wave + u) + 4 * q + r;
-        if (n < N && k < K) atomicAdd(a.dw + (long)n * K + k, acc[u][v][r]);
+        if (n < N && k < K) wg_out(dw + (long)n * K + k, acc[u][v][r], det);
       }
     }
 }
@@ -726,7 +728,9 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_tr_kernel(mds_pw_wgrad_args a
   const long mbeg = (long)split_id * rows_per_block;
   long mend = mbeg + rows_per_block;
   if (mend > a.M) mend = a.M;
-  if (mbeg >= a.M) return;   // (row splits are rounded up to a multiple of 8; whole block, before any barrier)
+  if (mbeg >= a.M) return;   // (row splits are rounded up to a multiple of 8; whole block, before any barrier; such a split has no slot: the slots are the cdiv(M, rows_per_block) real splits)
+  const bool det = a.partial.buf != nullptr;      // deterministic way out: this row split's slot, plain stores
+  float* const dw = wg_base(a.dw, a.partial, (long)a.N * a.K, split_id);
   const T* x = (const T*)a.x;
   const T* dy = (const T*)a.dy;
   const int kfr = (K - kt0 >= KT) ? KF : ((K - kt0 + 15) >> 4);
@@ -860,29 +864,26 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_tr_kernel(mds_pw_wgrad_args a
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int n = n0 + 16 * (NF * wave + u) + 4 * q + r;
-        if (n < N && k < K && !(dbg & 1)) atomicAdd(a.dw + (long)n * K + k, acc[u][v][r]);
+        if (n < N && k < K && !(dbg & 1)) wg_out(dw + (long)n * K + k, acc[u][v][r], det);
       }
     }
 }
 
-extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
-  MDS_REQUIRE(a && a->M > 0 && a->K > 0 && a->N > 0, "pw_wgrad: bad dims");
-  MDS_REQUIRE(a->K % 8 == 0 && a->N % 8 == 0, "pw_wgrad: K, N must be multiples of 8");
-  MDS_REQUIRE(a->x && a->dy && a->dw, "pw_wgrad: null pointer");
-  MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || a->pro.mode == MDS_PRO_GATE || (a->pro.scale && a->pro.shift), "pw_wgrad: prologue needs scale/shift");
-  MDS_REQUIRE((a->pro.mode != MDS_PRO_BN_SILU_GATE && a->pro.mode != MDS_PRO_GATE) || (a->pro.gate && a->pro.rows_per_group > 0), "pw_wgrad: gate prologue");
-  MDS_REQUIRE(a->M < 2147483647L, "pw_wgrad: M too large");
+// launch geometry of mds_pw_wgrad: the launcher and the partial-buffer query both come here
+struct PwWgGeo { bool tr; int tiles; long rpb, splits; };
+static PwWgGeo pw_wgrad_geo(const mds_pw_wgrad_args* a) {
+  PwWgGeo g;
   // Tile shape (NF, KF) = (2, 4): 128 x 64.  Wider tiles — (2,12) full-K, (2,8), (3,8) — cut the PMC
   // fetch from 2.6x to 1.5x of the algorithmic bytes but measured 15-80 % SLOWER (fewer blocks,
   // 2 instead of 3-4 waves/SIMD): the re-reads are L2/Infinity-Cache hits and occupancy matters more.
   const int NT = 128, KT = 64;
-  const int tiles = cdiv(a->N, NT) * cdiv(a->K, KT);
+  const int tiles = g.tiles = cdiv(a->N, NT) * cdiv(a->K, KT);
   // Split-M blocks: every block ends with one atomic per output value, so fewer, longer blocks win until the chip runs
   // dry.  Timed ALONE the optimum is ~400-500 blocks in total (1024: +25...50 %) - but these launches run on the second
   // stream beside the dependent chain, where every block they hold is a CU slot the critical kernel does not get:
   // inside the training step 128 blocks in total measured best (448: +0.25 ms per step, 896: +0.8 ms, 32...224: flat).
   // The multi-million-row layers still want <= 2048 rows per block.
-  const bool tr = a->dtype == MDS_BF16;     // the transposing-LDS-read kernel; fp32 takes the generic one
+  const bool tr = g.tr = a->dtype == MDS_BF16;     // the transposing-LDS-read kernel; fp32 takes the generic one
   long want_blocks = (mds_knob(MDS_KNOB_WG_BLOCKS) > 0 ? mds_knob(MDS_KNOB_WG_BLOCKS) : 192) / tiles;   // budget re-swept with the XCD-aligned splits: 128 / 192 / 224 / 288 -> 13.88 / 13.77 / 13.78 / 13.78 ms per step (was 128)
   if (want_blocks < a->M / 2048) want_blocks = a->M / 2048;
   if (tr && !(mds_knob(MDS_KNOB_WG_DBG) & 32)) {   // row splits in multiples of 8: split s and all its output tiles run on XCD s % 8 (see the kernel)
@@ -893,6 +894,28 @@ extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
   long rpb = (a->M + want_blocks - 1) / want_blocks;
   rpb = ((rpb + WG_ROWS - 1) / WG_ROWS) * WG_ROWS;
   if (rpb < 4 * WG_ROWS) rpb = 4 * WG_ROWS;
+  g.rpb = rpb; g.splits = cdiv(a->M, rpb);      // every split covers every output tile in full: splits slots of N * K floats
+  return g;
+}
+#define PW_WGRAD_DIMS_OK(a) \
+  MDS_REQUIRE(a && a->M > 0 && a->K > 0 && a->N > 0, "pw_wgrad: bad dims"); \
+  MDS_REQUIRE(a->K % 8 == 0 && a->N % 8 == 0, "pw_wgrad: K, N must be multiples of 8"); \
+  MDS_REQUIRE(a->M < 2147483647L, "pw_wgrad: M too large")
+extern "C" long mds_pw_wgrad_partial_floats(const mds_pw_wgrad_args* a) {
+  PW_WGRAD_DIMS_OK(a);
+  return wg_floats((long)a->N * a->K, pw_wgrad_geo(a).splits);
+}
+extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
+  PW_WGRAD_DIMS_OK(a);
+  MDS_REQUIRE(a->x && a->dy && a->dw, "pw_wgrad: null pointer");
+  MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || a->pro.mode == MDS_PRO_GATE || (a->pro.scale && a->pro.shift), "pw_wgrad: prologue needs scale/shift");
+  MDS_REQUIRE((a->pro.mode != MDS_PRO_BN_SILU_GATE && a->pro.mode != MDS_PRO_GATE) || (a->pro.gate && a->pro.rows_per_group > 0), "pw_wgrad: gate prologue");
+  const PwWgGeo g = pw_wgrad_geo(a);
+  MDS_PARTIAL_OK(a->partial, wg_floats((long)a->N * a->K, g.splits), "pw_wgrad");
+  MDS_REQUIRE(!(a->partial.buf && (mds_knob(MDS_KNOB_WG_DBG) & 7)), "pw_wgrad: MDS_KNOB_WG_DBG ablation bits %d leave slots unwritten: not with a partial buffer", mds_knob(MDS_KNOB_WG_DBG) & 7);
+  const int NT = 128, KT = 64, tiles = g.tiles;
+  const bool tr = g.tr;
+  const long rpb = g.rpb;
   dim3 grid(cdiv(a->M, rpb), tiles), block(256);
   if (tr) grid = dim3((unsigned)((cdiv(a->M, rpb) + 7) / 8 * 8 * tiles), 1);
 #define WG_GO(T, PRO) \
@@ -910,7 +933,8 @@ extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
       case MDS_PRO_GATE: WGT_GO(MDS_PRO_GATE); break;
       default: mds_set_error("pw_wgrad: prologue mode %d", a->pro.mode); return MDS_ERR_BAD_ARG;
     }
-    return mds_check_launch("pw_wgrad");
+    if (int rc = mds_check_launch("pw_wgrad")) return rc;
+    return wg_finish(a->partial, a->dw, (long)a->N * a->K, g.splits, stream);
   }
 #undef WGT_GO
   MDS_DISPATCH_DTYPE(a->dtype, T, {
@@ -924,5 +948,6 @@ extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
     }
   });
 #undef WG_GO
-  return mds_check_launch("pw_wgrad");
+  if (int rc = mds_check_launch("pw_wgrad")) return rc;
+  return wg_finish(a->partial, a->dw, (long)a->N * a->K, g.splits, stream);
 }

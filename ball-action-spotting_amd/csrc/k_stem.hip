@@ -151,6 +151,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(mds_stem_wgrad_args a) 
   for (int f = 0; f < 2; ++f)
 #pragma unroll
     for (int g = 0; g < 2; ++g) acc[f][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const bool det = a.partial.buf != nullptr;      // deterministic way out: every WAVE holds a whole filter gradient - slot = global wave index
+  float* const dw = wg_base(a.dw, a.partial, (long)a.Cout * 27, gw);
   for (long gi = gw; gi < ngroups; gi += nw) {
     const int gx = (int)(gi % gpr);
     long r = gi / gpr;
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(mds_stem_wgrad_args a) 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int oc = 16 * f + 4 * q + r;
-        if (k < 27 && oc < a.Cout) atomicAdd(a.dw + oc * 27 + k, acc[f][g][r]);
+        if (k < 27 && oc < a.Cout) wg_out(dw + oc * 27 + k, acc[f][g][r], det);
       }
     }
 }
@@ -359,6 +361,8 @@ __global__ __launch_bounds__(256, DYP ? 2 : 3) void stem_wgrad_tiled_kernel(mds_
   // which was most of this kernel's time)
   __syncthreads();
   float* red = (float*)smem;   // [4 waves][32 oc][32 k]
+  const bool det = a.partial.buf != nullptr;      // deterministic way out: slot = blockIdx.x
+  float* const dw = wg_base(a.dw, a.partial, (long)a.Cout * 27, blockIdx.x);
 #pragma unroll
   for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -368,7 +372,7 @@ __global__ __launch_bounds__(256, DYP ? 2 : 3) void stem_wgrad_tiled_kernel(mds_
   __syncthreads();
   for (int e = tid; e < 32 * 32; e += 256) {
     const int oc = e >> 5, k = e & 31;
-    if (k < 27 && oc < a.Cout) atomicAdd(a.dw + oc * 27 + k, (red[e] + red[1024 + e]) + (red[2048 + e] + red[3072 + e]));
+    if (k < 27 && oc < a.Cout) wg_out(dw + oc * 27 + k, (red[e] + red[1024 + e]) + (red[2048 + e] + red[3072 + e]), det);
   }
 }
 
@@ -505,9 +509,34 @@ static int stem_fwd_tiled(const mds_stem_fwd_args* a, mds_stream_t stream) {
   return mds_check_launch("stem_fwd");
 }
 
+// launch geometry of mds_stem_wgrad: the launcher and the partial-buffer query both come here
+struct StemWgGeo { int tiles_a, tiles_b, tpb; long blocks, slots; };
+static StemWgGeo stem_wgrad_geo(const mds_stem_wgrad_args* a) {
+  StemWgGeo g = {};
+  if (a->dtype == MDS_BF16) {
+    g.tiles_a = cdiv(a->OH, SW_ROWS); g.tiles_b = cdiv(a->OW, SW_COLS);
+    const long total = (long)a->N * g.tiles_a * g.tiles_b;
+    g.tpb = (int)cdiv(total, total < 768 ? total : 768);   // three blocks per CU
+    g.blocks = g.slots = cdiv(total, g.tpb);               // a block's four waves meet in LDS: one slot per block
+  } else {
+    const long ngroups = (long)a->N * a->OH * ((a->OW + 31) / 32);
+    g.blocks = (ngroups + 3) / 4;
+    if (g.blocks > 512) g.blocks = 512;
+    g.slots = 4 * g.blocks;                                // one slot per wave
+  }
+  return g;
+}
+#define STEM_WGRAD_DIMS_OK(a) \
+  MDS_REQUIRE(a && a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0, "stem_wgrad: bad dims"); \
+  MDS_REQUIRE(a->Cout % 16 == 0 && a->Cout <= 32, "stem_wgrad: Cout=%d must be 16 or 32", a->Cout)
+extern "C" long mds_stem_wgrad_partial_floats(const mds_stem_wgrad_args* a) {
+  STEM_WGRAD_DIMS_OK(a);
+  return wg_floats((long)a->Cout * 27, stem_wgrad_geo(a).slots);
+}
 extern "C" int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream) {
-  MDS_REQUIRE(a && a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0, "stem_wgrad: bad dims");
-  MDS_REQUIRE(a->Cout % 16 == 0 && a->Cout <= 32, "stem_wgrad: Cout=%d must be 16 or 32", a->Cout);
+  STEM_WGRAD_DIMS_OK(a);
+  const StemWgGeo sg = stem_wgrad_geo(a);
+  MDS_PARTIAL_OK(a->partial, wg_floats((long)a->Cout * 27, sg.slots), "stem_wgrad");
   const bool dyp = a->dyp.mode != 0;
   MDS_REQUIRE(a->x && (a->dy || dyp) && a->dw, "stem_wgrad: null pointer");
   if (dyp) {
@@ -516,17 +545,13 @@ extern "C" int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream)
                 "stem_wgrad: dy prologue needs u, y, bn, lin and a PLAIN or SILU gradient source");
   }
   if (a->dtype == MDS_BF16) {
-    const int tiles_a = cdiv(a->OH, SW_ROWS), tiles_b = cdiv(a->OW, SW_COLS);
-    const long total = (long)a->N * tiles_a * tiles_b;
-    const int tpb = (int)cdiv(total, total < 768 ? total : 768);   // three blocks per CU
+    const int tiles_a = sg.tiles_a, tiles_b = sg.tiles_b, tpb = sg.tpb;
     const size_t smem = (size_t)((2 * SW_ROWS + 1) * 9 + SW_ROWS * SW_COLS + 1) * SW_PITCH * sizeof(bf16_t);
-    if (dyp) MDS_LAUNCH(stem_wgrad_tiled_kernel<true>, dim3(cdiv(total, tpb)), dim3(256), smem, stream, *a, tiles_a, tiles_b, tpb);
-    else MDS_LAUNCH(stem_wgrad_tiled_kernel<false>, dim3(cdiv(total, tpb)), dim3(256), smem, stream, *a, tiles_a, tiles_b, tpb);
-    return mds_check_launch("stem_wgrad");
+    if (dyp) MDS_LAUNCH(stem_wgrad_tiled_kernel<true>, dim3((unsigned)sg.blocks), dim3(256), smem, stream, *a, tiles_a, tiles_b, tpb);
+    else MDS_LAUNCH(stem_wgrad_tiled_kernel<false>, dim3((unsigned)sg.blocks), dim3(256), smem, stream, *a, tiles_a, tiles_b, tpb);
+  } else {
+    MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(stem_wgrad_kernel<T>, dim3((unsigned)sg.blocks), dim3(256), 0, stream, *a));
   }
-  const long ngroups = (long)a->N * a->OH * ((a->OW + 31) / 32);
-  long nb = (ngroups + 3) / 4;
-  if (nb > 512) nb = 512;
-  MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(stem_wgrad_kernel<T>, dim3((unsigned)nb), dim3(256), 0, stream, *a));
-  return mds_check_launch("stem_wgrad");
+  if (int rc = mds_check_launch("stem_wgrad")) return rc;
+  return wg_finish(a->partial, a->dw, (long)a->Cout * 27, sg.slots, stream);
 }

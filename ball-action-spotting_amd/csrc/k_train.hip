@@ -34,16 +34,27 @@ __global__ __launch_bounds__(256) void focal_kernel(mds_focal_args a) {
     part = wave_sum(part);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(a.loss, ((red[0] + red[1]) + (red[2] + red[3])) * inv);
+    if (threadIdx.x == 0) wg_out(wg_base(a.loss, a.partial, 1, blockIdx.x), ((red[0] + red[1]) + (red[2] + red[3])) * inv, a.partial.buf != nullptr);      // deterministic way out: slot = block
   }
+}
+static int focal_blocks(const mds_focal_args* a) { const int b = cdiv(a->n, 256); return b > 1024 ? 1024 : b; }
+// one block (n <= 256, every head of this network) adds once to the zeroed accumulator: nothing to order, no buffer needed
+extern "C" long mds_focal_fwd_bwd_partial_floats(const mds_focal_args* a) {
+  MDS_REQUIRE(a && a->n > 0, "focal_fwd_bwd: bad args");
+  const int blocks = focal_blocks(a);
+  return a->reduction == MDS_REDUCE_NONE || blocks == 1 ? 0 : wg_floats(1, blocks);
 }
 extern "C" int mds_focal_fwd_bwd(const mds_focal_args* a, mds_stream_t stream) {
   MDS_REQUIRE(a && a->n > 0 && a->x && a->t && a->loss && a->dx, "focal_fwd_bwd: bad args");
   MDS_REQUIRE(a->reduction >= MDS_REDUCE_NONE && a->reduction <= MDS_REDUCE_SUM, "focal_fwd_bwd: reduction");
-  int blocks = cdiv(a->n, 256);
-  if (blocks > 1024) blocks = 1024;
-  MDS_LAUNCH(focal_kernel, dim3(blocks), dim3(256), 0, stream, *a);
-  return mds_check_launch("focal_fwd_bwd");
+  const int blocks = focal_blocks(a);
+  const bool det = a->partial.buf && a->reduction != MDS_REDUCE_NONE;
+  MDS_REQUIRE(!det || (a->partial.floats >= wg_floats(1, blocks) && ((uintptr_t)a->partial.buf & 15) == 0), "focal_fwd_bwd: partial buffer of %ld floats, the launch needs %ld (16-byte aligned)", a->partial.floats, wg_floats(1, blocks));
+  mds_focal_args k = *a;
+  if (!det) k.partial.buf = nullptr;
+  MDS_LAUNCH(focal_kernel, dim3(blocks), dim3(256), 0, stream, k);
+  if (int rc = mds_check_launch("focal_fwd_bwd")) return rc;
+  return det ? wg_finish(a->partial, a->loss, 1, blocks, stream) : 0;
 }
 
 // ------------------------------------------------------------------ multi-tensor AdamW / EMA

@@ -163,6 +163,22 @@ MDS_DEV unsigned xcd_contiguous(unsigned id, unsigned n) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
 }
 
+// ------------------------------------------------------------------ deterministic way out (mds_partial_t, include/mds.h)
+// A kernel that ends in fp32 atomics on a result of `numel` floats takes the launch's mds_partial_t by value: where it added
+// v to result[e] it calls wg_out(wg_base(result, partial, numel, slot) + e, v, det) - a plain store to the block's own slot when
+// the buffer is set (det, block-uniform), the atomic of before when not.  The host side of every family:
+//   need = wg_floats(numel, slots)   (query and capacity check)   ...launch...   wg_finish(partial, result, numel, slots, stream)
+MDS_DEV long wg_stride(long numel) { return (numel + 3) & ~3L; }
+MDS_DEV float* wg_base(float* result, const mds_partial_t& pt, long numel, long slot) { return pt.buf ? pt.buf + slot * wg_stride(numel) : result; }
+MDS_DEV void wg_out(float* p, float v, bool det) {
+  if (det) *p = v;
+  else atomicAdd(p, v);
+}
+static inline long wg_floats(long numel, long slots) { return ((numel + 3) & ~3L) * slots; }
+int wg_finish(const mds_partial_t& pt, float* result, long numel, long slots, mds_stream_t stream);   // k_det.hip; 0 or MDS_ERR_*
+#define MDS_PARTIAL_OK(pt, need, what) \
+  MDS_REQUIRE(!(pt).buf || ((pt).floats >= (need) && ((uintptr_t)(pt).buf & 15) == 0), what ": partial buffer of %ld floats, the launch needs %ld (16-byte aligned)", (long)(pt).floats, (long)(need))
+
 // ------------------------------------------------------------------ developer knobs
 int mds_knob(int id);   // mds_dev_set() values (0 = default), see include/mds.h
 

@@ -64,10 +64,12 @@ def _parse_header(path: str):
                 fields.append((nm, ctype))
         structs[name] = type(name, (C.Structure,), {"_fields_": fields})
     funcs = re.findall(r"^\s*int\s+(mds_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
-    return defines, structs, funcs
+    # the deterministic-mode family (mds_<op>_partial_floats, mds_wgrad_finish) returns long: a float count or a negative code
+    long_funcs = re.findall(r"^\s*long\s+(mds_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
+    return defines, structs, funcs, long_funcs
 
 
-DEFINES, STRUCTS, FUNCS = _parse_header(HEADER)
+DEFINES, STRUCTS, FUNCS, LONG_FUNCS = _parse_header(HEADER)
 globals().update(DEFINES)
 
 
@@ -101,7 +103,7 @@ class Lib:
             raise MdsError(f"{path}: ABI version {self.dll.mds_version()} != header {DEFINES['MDS_VERSION']}")
         self.fn = {}
         self.missing = []
-        for name, params in FUNCS:
+        for name, params in FUNCS + LONG_FUNCS:
             if name == "mds_version":
                 continue
             try:
@@ -109,11 +111,11 @@ class Lib:
             except AttributeError:
                 self.missing.append(name)   # tests assert this list is empty
                 continue
-            f.restype = C.c_int
+            f.restype = C.c_long if (name, params) in LONG_FUNCS else C.c_int
             self.fn[name[4:]] = f
         # argument types of EVERY entry point come from the header's own prototypes: an untyped ctypes call passes a Python int as a
         # 32-bit C int, which truncates a hipStream_t (any stream but the null stream) and crashes inside the launch
-        for name, params in FUNCS:
+        for name, params in FUNCS + LONG_FUNCS:
             if name[4:] in self.fn:
                 self.fn[name[4:]].argtypes = [_ctype_of(p) for p in params.split(",")] if params.strip() != "void" else []
 

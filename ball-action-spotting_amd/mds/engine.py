@@ -204,7 +204,7 @@ class Plan:
     """The recorded schedules + buffers for one configuration."""
 
     def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False,
-                 eval_se_fusion=False, eval_er_fusion=False):
+                 eval_se_fusion=False, eval_er_fusion=False, deterministic=False):
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
                                     # tail plans: ("probs", tta) - the head also writes the TTA-mean of the sigmoids (mds.predict)
@@ -236,6 +236,12 @@ class Plan:
         # MultiDimStacker.eval_er_fusion: the edge-residual blocks of an inference plan run their 3x3 expansion and their 1x1
         # projection in one launch (mds_project_t) - no mid-wide ya tensor, no projection pw_fwd
         self.eval_er_fusion = bool(eval_er_fusion) and self.eval_epilogues
+        # MultiDimStacker.deterministic: every launch of the backward schedule that ends in fp32 atomics on a parameter gradient takes
+        # the fixed-order way out (mds_partial_t): slots in a workspace + the finishing kernel, issued by the same entry point on the
+        # same stream - so the finish is on the producer's stream, before the gradient-bucket cut and join_backward, by construction.
+        # Plans without a backward schedule have no such launch: they ignore the switch.
+        self.deterministic = bool(deterministic) and need_grad
+        self.det_workspace_bytes = 0
         self.in_flight = False
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
@@ -890,6 +896,7 @@ class Plan:
                 a.tensor = raw[off:off + size(a)].view(a.dtype)
                 off += pad(size(a))
             return raw
+        self._bind_partials()
         self._zero_fwd = carve(self.zf64_arena, self.zf_arena)
         self._zero_bwd = carve(self.zb64_arena, self.zb_arena, self.grad_arena)
         for l in self._lazy:
@@ -937,6 +944,41 @@ class Plan:
             self.bound[seg] = out
             self.costs[seg] = [op_cost(name, kw, 2 if self.code == cabi.MDS_BF16 else 4) for name, kw in ops]
         self.nbytes = sum(l.tensor.numel() * l.tensor.element_size() for l in self._lazy)
+
+    # launches that add into a parameter gradient with fp32 atomics, i.e. that have an mds_partial_t and an mds_<op>_partial_floats
+    DET_OPS = ("pw_wgrad", "conv_wgrad", "stem_wgrad", "dw_bwd", "gem_bwd")
+    def _bind_partials(self):
+        """deterministic plans: ask the library how many floats of partial buffer each weight-gradient launch needs (the
+        launcher's own geometry code) and give every such launch the workspace of its stream - the launches of one stream run
+        one after the other, finish included, so they share one buffer sized for the largest"""
+        if not self.deterministic:
+            return
+        ws = {False: self._own(0, torch.float32), True: self._own(0, torch.float32)}       # chain stream / weight-gradient stream
+        for seg, ops in self.segs.items():
+            for name, kw in ops:
+                if name not in self.DET_OPS:
+                    continue
+                st = self._bind_dims(kw.get("_struct", f"mds_{name}_args"), kw)
+                n = int(self.lib.fn[name + "_partial_floats"](C.byref(st)))
+                if n < 0:
+                    self.lib.check(n, name + "_partial_floats")
+                side = name in self.SIDE_OPS or bool(kw.get("_side"))
+                ws[side].numel = max(ws[side].numel, n)
+                kw["partial"] = dict(_struct="mds_partial_t", buf=ws[side], floats=n)
+        self.det_workspace_bytes = 4 * (ws[False].numel + ws[True].numel)
+
+    def _bind_dims(self, struct_name, kw):
+        """the struct of a recorded launch with its scalars only (buffers are not allocated yet): what the geometry queries read"""
+        vals = {}
+        for k, v in kw.items():
+            if k.startswith("_"):
+                continue
+            if isinstance(v, dict):
+                v = self._bind_dims(v.get("_struct", "mds_pro_t"), v)
+            elif isinstance(v, (Lazy, P)) or hasattr(v, "data_ptr"):
+                v = None
+            vals[k] = v
+        return cabi.make(struct_name, **vals)
 
     def _bind(self, struct_name, kw):
         vals = {}

@@ -397,6 +397,7 @@ class MultiDimStacker(nn.Module):
         self.eval_fusion = False              # eval + no-grad plans: the 2D blocks' 1x1 expansion runs inside the depthwise launch
         self.eval_se_fusion = False           # eval + no-grad plans: the pooling depthwise launch also computes the squeeze-excite gate
         self.eval_er_fusion = False           # eval + no-grad plans: the edge-residual blocks' 3x3 expansion and 1x1 projection run in one launch
+        self.deterministic = False            # training plans: weight gradients summed in a fixed order (bit-identical reruns of a step)
         self._cache = _PlanCache()
         self._lib: Optional[cabi.Lib] = None  # tests inject the kernel simulator here; product: cabi.load()
         self._mask_override = None            # parity tests: host-supplied DropPath/dropout masks
@@ -467,7 +468,8 @@ class MultiDimStacker(nn.Module):
         fusion = bool(getattr(self, "eval_fusion", False))     # (a module unpickled from before the attribute existed: off)
         se_fusion = bool(getattr(self, "eval_se_fusion", False))
         er_fusion = bool(getattr(self, "eval_er_fusion", False))
-        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion, se_fusion, er_fusion)
+        det = bool(getattr(self, "deterministic", False)) and need_grad      # (plans without a backward schedule ignore the switch)
+        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion, se_fusion, er_fusion, det)
         cache = self._cache
         pool = cache.plans.setdefault(key, [])
         cache.plans.move_to_end(key)
@@ -476,7 +478,7 @@ class MultiDimStacker(nn.Module):
                 return plan
         pool[:] = [p for p in pool if not p.stale()]
         plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, eval_fusion=fusion,
-                    eval_se_fusion=se_fusion, eval_er_fusion=er_fusion)
+                    eval_se_fusion=se_fusion, eval_er_fusion=er_fusion, deterministic=det)
         pool.append(plan)
         cache.evict(key)
         return plan

@@ -42,7 +42,7 @@ def _stream(t: torch.Tensor):
 # ------------------------------------------------------------------------------------------------ focal loss
 class _Focal(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, inputs, targets, alpha, gamma, reduction):
+    def forward(ctx, inputs, targets, alpha, gamma, reduction, deterministic=False):
         x = inputs.detach().float().contiguous()
         t = targets.detach().float().contiguous()
         assert x.shape == t.shape, "focal loss: inputs and targets must have the same shape"
@@ -53,6 +53,14 @@ class _Focal(torch.autograd.Function):
         lib = _lib(x)
         with torch.cuda.device(x.device) if x.is_cuda else _null():
             args = cabi.make("mds_focal_args", n=n, x=x, t=t, alpha=float(alpha), gamma=float(gamma), reduction=red, loss=loss, dx=dx)
+            if deterministic or isinstance(deterministic, dict):      # more than one block adds to the loss value (n > 256): their terms go through slots, added in block order
+                need = int(lib.fn["focal_fwd_bwd_partial_floats"](C.byref(args)))
+                if need > 0:       # `deterministic` may be a dict: the caller's workspace cache (FocalLoss keeps one - nothing allocated in steady state)
+                    cache = deterministic if isinstance(deterministic, dict) else {}
+                    part = cache.get("partial")
+                    if part is None or part.numel() < need or part.device != x.device:
+                        part = cache["partial"] = torch.empty(need, dtype=torch.float32, device=x.device)
+                    args.partial = cabi.make("mds_partial_t", buf=part, floats=need)
             lib.check(lib.fn["focal_fwd_bwd"](C.byref(args), _stream(x)), "focal_fwd_bwd")
         ctx.save_for_backward(dx)
         ctx.in_dtype = inputs.dtype
@@ -61,7 +69,7 @@ class _Focal(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         (dx,) = ctx.saved_tensors
-        return (dx * gout).to(ctx.in_dtype), None, None, None, None
+        return (dx * gout).to(ctx.in_dtype), None, None, None, None, None
 
 
 class _null:
@@ -72,18 +80,22 @@ class _null:
         return False
 
 
-def sigmoid_focal_loss(inputs, targets, alpha: float = -1.0, gamma: float = 2.0, reduction: str = "mean"):
-    """src/losses.py:5-50 — value and gradient from one kernel."""
-    return _Focal.apply(inputs, targets, alpha, gamma, reduction)
+def sigmoid_focal_loss(inputs, targets, alpha: float = -1.0, gamma: float = 2.0, reduction: str = "mean", deterministic: bool = False):
+    """src/losses.py:5-50 — value and gradient from one kernel.  `deterministic`: a reduced loss over more than 256 elements is
+    summed in block order instead of by atomics (up to 256 elements - every head of this network - one block computes it: always
+    repeatable, nothing changes).  The functional form allocates that workspace per call; `FocalLoss` keeps it."""
+    return _Focal.apply(inputs, targets, alpha, gamma, reduction, deterministic)
 
 
 class FocalLoss(nn.Module):
-    def __init__(self, alpha: float = -1.0, gamma: float = 2.0, reduction: str = "mean"):
+    def __init__(self, alpha: float = -1.0, gamma: float = 2.0, reduction: str = "mean", deterministic: bool = False):
         super().__init__()
-        self.alpha, self.gamma, self.reduction = alpha, gamma, reduction
+        self.alpha, self.gamma, self.reduction, self.deterministic = alpha, gamma, reduction, deterministic
+        self._det_ws = {}      # the slot workspace of a deterministic loss over more than 256 elements, allocated on first use
 
     def forward(self, inputs, targets):
-        return sigmoid_focal_loss(inputs, targets, alpha=self.alpha, gamma=self.gamma, reduction=self.reduction)
+        return sigmoid_focal_loss(inputs, targets, alpha=self.alpha, gamma=self.gamma, reduction=self.reduction,
+                                  deterministic=self.__dict__.setdefault("_det_ws", {}) if getattr(self, "deterministic", False) else False)
 
 
 # ------------------------------------------------------------------------------------------------ tables

@@ -24,7 +24,8 @@
  *    run-dependent order (round 2); in fp64 the cross-block accumulation is exact to 1e-16 and order-independent.
  *    The same holds for the other cross-block sums that feed activations or their gradients - the squeeze-excite pool
  *    (`pooled`), its backward (`dgate`) and the row-split GeM accumulators: all fp64.  What is left to fp32 atomics
- *    are the parameter-gradient accumulations (weight-gradient arena, GeM's dp), which feed nothing else in the step.
+ *    are the parameter-gradient accumulations (weight-gradient arena, GeM's dp), which feed nothing else in the step -
+ *    and those have a second, fixed-order way out (mds_partial_t below) for runs that must repeat bit for bit.
  */
 #ifndef MDS_H
 #define MDS_H
@@ -32,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 135
+#define MDS_VERSION 136
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -79,6 +80,42 @@ int mds_dev_set(int knob, int value);
  * tools/probes/event_cost.py; 71 of them per training step), a stop event nothing.  Returns the number of launches that were
  * issued with the previously armed event (0 after an op that launched nothing: that event must not be waited on).            */
 int mds_launch_event(void* event);
+
+/* ---- deterministic way out of the kernels that end in fp32 atomics (the weight gradients, GeM's dp, the loss value).
+ * With buf != NULL a block does not add its contribution to the result with atomicAdd: it STORES it to its own slot of the
+ * caller-owned fp32 buffer, buf[slot * stride + e] with e the element's index in the result and stride = numel rounded up to
+ * a multiple of 4.  The slot is a pure function of the launch geometry (block / split / wave index, never an arrival order
+ * or a ticket), every slot is written in full by the launch, and the SAME entry point then issues the finishing kernel on the
+ * same stream: result[e] += (the slots' values added in slot order, in the fixed grouping of mds_wgrad_finish).  Two runs of a
+ * launch on the same device, library build and knob settings give the same bits.  buf == NULL: today's atomic path, bit for bit
+ * the code of before.  `floats` is the buffer's capacity; mds_<op>_partial_floats(args) says what a launch of those args
+ * needs (same geometry code as the launcher; only dims, dtype, prologue mode and knobs matter, pointers may be NULL) and a
+ * launch given less returns MDS_ERR_BAD_ARG.  The buffer needs no initialisation, must be 16-byte aligned, and can be shared
+ * by all launches of one stream.  The entry points of this family - the queries and mds_wgrad_finish - return `long`: a
+ * count of floats (>= 0), or a negative MDS_ERR_* code.                                                                    */
+typedef struct {
+  float* buf;      /* NULL: off */
+  long floats;     /* capacity of buf */
+} mds_partial_t;
+/* the finishing kernel on its own: dst[e] += sum over s < slots of partial[s * slot_stride + e], e < numel.  Order: the slots are cut
+ * into G contiguous ranges of ceil(slots / G); each range is summed first to last, the range sums are added first to last, the
+ * total is added to dst.  G depends on numel only: MDS_FINISH_GROUPS for results of MDS_FINISH_WIDE floats and more (a streaming
+ * reduce: the parallelism is in the columns), MDS_FINISH_GROUPS_MID from MDS_FINISH_MID floats, MDS_FINISH_GROUPS_SMALL below (a
+ * depthwise filter, the stem, GeM's exponent: a few thousand floats in hundreds of slots - the parallelism is in the slot ranges).
+ * 16-byte loads, four slots in flight per lane.  slot_stride % 4 == 0, partial 16-byte aligned.  Returns 0, or a negative MDS_ERR_* code. */
+#define MDS_FINISH_GROUPS 4
+#define MDS_FINISH_GROUPS_MID 16
+#define MDS_FINISH_GROUPS_SMALL 64
+#define MDS_FINISH_WIDE 65536
+#define MDS_FINISH_MID 4096
+typedef struct {
+  const float* partial;
+  float* dst;
+  long numel;
+  long slots;
+  long slot_stride;
+} mds_wgrad_finish_args;
+long mds_wgrad_finish(const mds_wgrad_finish_args* a, mds_stream_t stream);
 
 /* ---- output transform ("epilogue") for plans that KNOW the BatchNorm statistics before the producer runs (eval mode /
  * the predictor): the producer stores act(acc*scale[c] + shift[c]) instead of the raw convolution output, so no consumer
@@ -205,8 +242,10 @@ typedef struct {
   const void* dy; /* [M][N]                                      */
   float* dw;      /* [N][K] fp32                                 */
   mds_pro_t pro;
+  mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_pw_wgrad_args;
 int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream);
+long mds_pw_wgrad_partial_floats(const mds_pw_wgrad_args* a);   /* floats of partial.buf a launch of these args needs */
 
 /* ---- projection tail of the dense 3x3 forward (inference plans; mds_conv_fwd_args.project): the 1x1 projection that
  * follows the 3x3 expansion of an edge-residual block runs in the same launch (k_c3p.hip).  Per output pixel
@@ -281,8 +320,10 @@ typedef struct {
   const void* dyt; /* [N][OH][OW][Cout] */
   float* dw;
   mds_pro_t pro;
+  mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_conv_wgrad_args;
 int mds_conv_wgrad(const mds_conv_wgrad_args* a, mds_stream_t stream);
+long mds_conv_wgrad_partial_floats(const mds_conv_wgrad_args* a);
 
 /* ---- stem: 3x3 stride-2 TF-SAME convolution of the fp32 frame triple (Cin = stack_size = 3
  * planes, NCHW as produced by x.view(b*S, 3, h, w), multidim_stacker.py:214) -> channels-last.  */
@@ -319,8 +360,10 @@ typedef struct {
   mds_dyp_t dyp;  /* dyp.mode == 1: dy is formed on load from the stem BatchNorm's backward inputs (`dy` ignored):
                      dy = A*g + B*y + D with g = u (MDS_G_PLAIN) or u*silu'(y*scale + shift) (MDS_G_SILU) - the stem has no
                      data gradient, so its BatchNorm-backward apply pass would only feed this kernel (bf16 path)          */
+  mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_stem_wgrad_args;
 int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream);
+long mds_stem_wgrad_partial_floats(const mds_stem_wgrad_args* a);
 
 /* ---- expansion prologue of the 2D depthwise forward (inference plans; mds_dw_fwd_args.expand): the block's narrow
  * input x is expanded in the same launch, y1 = silu((x * w^T)[c] * scale[c] + shift[c]), one tile of output pixels and
@@ -402,8 +445,10 @@ typedef struct {
   const float* mean;  /* [C] of x's BN (for xhat)    */
   const float* rstd;
   double* stats;      /* fp64 [SLOTS][2][C]: sum g, sum g*xhat */
+  mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_dw_bwd_args;
 int mds_dw_bwd(const mds_dw_bwd_args* a, mds_stream_t stream);
+long mds_dw_bwd_partial_floats(const mds_dw_bwd_args* a);
 
 /* ---- K7: BatchNorm statistics -> per-channel affine (+ running-stat update, momentum, unbiased
  * running variance, num_batches_tracked += 1): torch.nn.functional.batch_norm semantics used by
@@ -629,8 +674,10 @@ typedef struct {
   void* u;              /* [rows][C] */
   float* dp;            /* [1] += */
   double* accum;        /* optional caller-zeroed fp64 [groups][C] (sum of c^p log c), as in mds_gem_fwd */
+  mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_gem_bwd_args;
 int mds_gem_bwd(const mds_gem_bwd_args* a, mds_stream_t stream);
+long mds_gem_bwd_partial_floats(const mds_gem_bwd_args* a);
 
 /* ---- K12: dropout (host-supplied scaled mask) + Linear  (multidim_stacker.py:232-237)        */
 typedef struct {
@@ -674,8 +721,10 @@ typedef struct {
   int reduction;
   float* loss;         /* [1] caller-zeroed accumulator (MEAN / SUM), or [n] (NONE) */
   float* dx;           /* [n] d loss / d x (for NONE: d l_i / d x_i)                 */
+  mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_focal_args;
 int mds_focal_fwd_bwd(const mds_focal_args* a, mds_stream_t stream);
+long mds_focal_fwd_bwd_partial_floats(const mds_focal_args* a);   /* 0: one block - the launch is deterministic without a buffer */
 
 /* Multi-tensor AdamW (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a
  * device-resident table of tensors in ONE launch; src/argus_models.py:62 `scaler.step(self.optimizer)`.
