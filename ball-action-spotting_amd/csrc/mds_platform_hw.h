@@ -161,6 +161,13 @@ MDS_DEV void sreg_pin(f32x8& v) { asm volatile("" : "+s"(v)); }
 // neither a vector register per lane nor an entry on vmcnt
 MDS_DEV float ld_uniform(const float* p, int idx) { return ((const __attribute__((address_space(4))) float*)(uintptr_t)p)[idx]; }
 
+// a blocking copy of `bytes` of device memory into a host buffer, ordered after the work already on `stream`: for argument
+// checks that must see a device-resident table (mds_mask_fill's keep[] when the caller has not vouched for it) - never on a hot path
+inline int mds_read_back(void* dst, const void* src, size_t bytes, hipStream_t stream) {
+  if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess) return -1;
+  return hipStreamSynchronize(stream) == hipSuccess ? 0 : -1;
+}
+
 // CUs of the current device (launch-shape rules that count rounds of the chip), asked once per device id; racing first
 // askers store the same value
 inline int mds_cu_count() {

@@ -23,6 +23,7 @@ HIP_LIB = os.path.join(PKG_ROOT, "csrc", "libmds_hip.so")
 
 _SCALARS = {
     "int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "long long": C.c_longlong, "unsigned char": C.c_ubyte,
+    "unsigned long long": C.c_ulonglong, "unsigned int": C.c_uint,
 }
 
 
@@ -64,7 +65,8 @@ def _parse_header(path: str):
                 fields.append((nm, ctype))
         structs[name] = type(name, (C.Structure,), {"_fields_": fields})
     funcs = re.findall(r"^\s*int\s+(mds_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
-    # the deterministic-mode family (mds_<op>_partial_floats, mds_wgrad_finish) returns long: a float count or a negative code
+    # the deterministic-mode family (mds_<op>_partial_floats, mds_wgrad_finish) returns long: a float count or a negative code;
+    # so does mds_mask_fill (0 or a negative code)
     long_funcs = re.findall(r"^\s*long\s+(mds_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
     return defines, structs, funcs, long_funcs
 

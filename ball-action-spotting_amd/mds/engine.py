@@ -204,7 +204,7 @@ class Plan:
     """The recorded schedules + buffers for one configuration."""
 
     def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False,
-                 eval_se_fusion=False, eval_er_fusion=False, deterministic=False):
+                 eval_se_fusion=False, eval_er_fusion=False, deterministic=False, device_rng=False):
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
                                     # tail plans: ("probs", tta) - the head also writes the TTA-mean of the sigmoids (mds.predict)
@@ -242,6 +242,9 @@ class Plan:
         # Plans without a backward schedule have no such launch: they ignore the switch.
         self.deterministic = bool(deterministic) and need_grad
         self.det_workspace_bytes = 0
+        # MultiDimStacker.device_rng: begin_forward fills the mask arena with one mds_mask_fill launch from the (seed, stream, draw)
+        # the module hands it, instead of two launches on torch's generator.  Plans without masks ignore the switch (set in _finalize).
+        self.device_rng = bool(device_rng) and training
         self.in_flight = False
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
@@ -906,6 +909,13 @@ class Plan:
             for off, n, kp in self.masks:
                 keep[off:off + n] = kp
             self.mask_keep = keep.to(dev)
+            # the fill of a device_rng plan: the table is checked here, on the host, so the launch never reads it back (a table
+            # with a value outside (0, 1] is left to the library, which reads it and refuses it)
+            self._fill_args = cabi.make("mds_mask_fill_args", mask=self.mask_arena.tensor, keep=self.mask_keep, n=self._mask_total,
+                                        keep_checked=int(bool(((keep > 0) & (keep <= 1)).all())))
+            self._fill_ref = C.byref(self._fill_args)
+        else:
+            self.device_rng = False
         # weight-pack job table (device resident)
         Job = cabi.STRUCTS["mds_pack_job"]
         jobs = (Job * max(len(self.pack_jobs), 1))()
@@ -1209,13 +1219,21 @@ class Plan:
                                                         self._stream()), "bn_eval_table")
         self.pack_weights()
 
-    def begin_forward(self, mask_override=None, refresh=True):
-        """refresh=False (the stream predictor): the caller runs refresh_weights() itself, and only when a parameter changed"""
+    def begin_forward(self, mask_override=None, refresh=True, rng=None):
+        """refresh=False (the stream predictor): the caller runs refresh_weights() itself, and only when a parameter changed.
+        rng = (seed, stream, draw): the masks come from mds_mask_fill (include/mds.h has the definition of every element) and
+        torch's generator is not touched; a mask_override still wins; plans without masks ignore it."""
         if self.zf_arena.numel or self.zf64_arena.numel:
             self._memset(self._zero_fwd)
         if self.masks:
             if mask_override is not None:
                 self.mask_arena.tensor.copy_(mask_override.to(self.device, torch.float32).view(-1))
+            elif rng is not None:
+                a = self._fill_args
+                a.seed, a.stream, a.draw = rng
+                rc = self.lib.fn["mask_fill"](self._fill_ref, self._stream())
+                if rc:
+                    self.lib.check(rc, "mask_fill")
             else:       # Bernoulli(keep) / keep in two launches (was five: rand, compare, cast, divide, copy)
                 self.mask_arena.tensor.bernoulli_(self.mask_keep).div_(self.mask_keep)
         if refresh:

@@ -105,7 +105,7 @@ class _MDSFunction(torch.autograd.Function):
         ctx.generation = plan.generation
         with plan.device_guard():
             plan.bind_input(x)
-            plan.begin_forward(module._mask_override)
+            plan.begin_forward(module._mask_override, rng=module._draw(plan))
             plan.run("f2d"); plan.run("f3d"); plan.run("fhead")
             B = x.shape[0]
             return plan.logits.tensor.view(B, -1).clone()
@@ -143,7 +143,7 @@ class _TailFunction(torch.autograd.Function):
         b, s, c, h, w = feats.shape
         with plan.device_guard():
             plan.feat.tensor.view(b, s, h, w, c).copy_(feats.detach().permute(0, 1, 3, 4, 2))
-            plan.begin_forward(module._mask_override)
+            plan.begin_forward(module._mask_override, rng=module._draw(plan))
             plan.run("f3d"); plan.run("fhead")
             return plan.logits.tensor.view(b, -1).clone()
 
@@ -253,7 +253,7 @@ def _op_forward(x: torch.Tensor, params: List[torch.Tensor], handle: int, need_g
         plan.generation += 1
     with plan.device_guard():
         plan.bind_input(x)
-        plan.begin_forward(m._mask_override)
+        plan.begin_forward(m._mask_override, rng=m._draw(plan))
         plan.run("f2d"); plan.run("f3d"); plan.run("fhead")
         return plan.logits.tensor.view(b, -1).clone(), torch.tensor(token, dtype=torch.int64)
 
@@ -398,6 +398,10 @@ class MultiDimStacker(nn.Module):
         self.eval_se_fusion = False           # eval + no-grad plans: the pooling depthwise launch also computes the squeeze-excite gate
         self.eval_er_fusion = False           # eval + no-grad plans: the edge-residual blocks' 3x3 expansion and 1x1 projection run in one launch
         self.deterministic = False            # training plans: weight gradients summed in a fixed order (bit-identical reruns of a step)
+        self.device_rng = False               # training plans: DropPath / dropout masks from the engine's own Philox stream (mds_mask_fill)
+        self.rng_seed = None                  # device_rng: None until the first drawing forward takes torch.initial_seed(); seed_rng() sets it
+        self.rng_stream = 0                   # device_rng: mds.parallel sets the rank, so that ranks sharing a seed draw different masks
+        self.rng_draws = 0                    # device_rng: forwards that filled a mask arena so far = the draw number of the next one
         self._cache = _PlanCache()
         self._lib: Optional[cabi.Lib] = None  # tests inject the kernel simulator here; product: cabi.load()
         self._mask_override = None            # parity tests: host-supplied DropPath/dropout masks
@@ -469,7 +473,8 @@ class MultiDimStacker(nn.Module):
         se_fusion = bool(getattr(self, "eval_se_fusion", False))
         er_fusion = bool(getattr(self, "eval_er_fusion", False))
         det = bool(getattr(self, "deterministic", False)) and need_grad      # (plans without a backward schedule ignore the switch)
-        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion, se_fusion, er_fusion, det)
+        dev_rng = bool(getattr(self, "device_rng", False)) and self.training     # (eval plans have no masks)
+        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion, se_fusion, er_fusion, det, dev_rng)
         cache = self._cache
         pool = cache.plans.setdefault(key, [])
         cache.plans.move_to_end(key)
@@ -478,10 +483,36 @@ class MultiDimStacker(nn.Module):
                 return plan
         pool[:] = [p for p in pool if not p.stale()]
         plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, eval_fusion=fusion,
-                    eval_se_fusion=se_fusion, eval_er_fusion=er_fusion, deterministic=det)
+                    eval_se_fusion=se_fusion, eval_er_fusion=er_fusion, deterministic=det, device_rng=dev_rng)
         pool.append(plan)
         cache.evict(key)
         return plan
+
+    # ------------------------------------------------------------------ device_rng: the module's own mask stream
+    def seed_rng(self, seed: int):
+        """fix the seed of the mask stream and restart it at draw 0"""
+        self.rng_seed, self.rng_draws = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+
+    def rng_state(self):
+        """what a checkpoint needs to resume the mask sequence (seed is None before the first drawing forward or seed_rng())"""
+        return dict(seed=getattr(self, "rng_seed", None), stream=int(getattr(self, "rng_stream", 0)), draws=int(getattr(self, "rng_draws", 0)))
+
+    def set_rng_state(self, state):
+        seed = state["seed"]
+        self.rng_seed = None if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.rng_stream, self.rng_draws = int(state["stream"]) & 0xFFFFFFFF, int(state["draws"])
+
+    def _draw(self, plan):
+        """(seed, stream, draw) for the forward about to be issued on `plan` and the counter moves on - or None: the plan draws
+        nothing from the module's stream (no masks, the switch is off, or a test injects the masks).  The draw number counts
+        drawing forwards only: it does not depend on which cached plan runs."""
+        if not plan.device_rng or self._mask_override is not None:
+            return None
+        if getattr(self, "rng_seed", None) is None:       # torch.manual_seed still governs a run that never calls seed_rng()
+            self.rng_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        draw = int(getattr(self, "rng_draws", 0))
+        self.rng_draws = draw + 1
+        return self.rng_seed, int(getattr(self, "rng_stream", 0)) & 0xFFFFFFFF, draw
 
     # ------------------------------------------------------------------ reference API
     def forward(self, x):
@@ -501,7 +532,7 @@ class MultiDimStacker(nn.Module):
             return _MDSFunction.apply(x, self, plan, *plan.params)
         with plan.device_guard():
             plan.bind_input(x)
-            plan.begin_forward(self._mask_override)
+            plan.begin_forward(self._mask_override, rng=self._draw(plan))
             plan.run("f2d"); plan.run("f3d"); plan.run("fhead")
             return plan.logits.tensor.view(b, -1).clone()
 
@@ -523,14 +554,14 @@ class MultiDimStacker(nn.Module):
             if kind == "2d":
                 b, t, h, w = x.shape
                 plan.bind_input(x)
-                plan.begin_forward(self._mask_override)
+                plan.begin_forward(self._mask_override, rng=self._draw(plan))
                 plan.run("f2d")
                 f = plan.feat.tensor.view(b, t // self.stack_size, plan.h, plan.w, self.num_3d_features)
                 return f.permute(0, 1, 4, 2, 3).float().contiguous()      # (b, S, 192, h, w) like the reference
             if kind == "3d":
                 b, t, c, h, w = x.shape
                 plan.feat.tensor.view(b, t, h, w, c).copy_(x.detach().permute(0, 1, 3, 4, 2))
-                plan.begin_forward(self._mask_override)
+                plan.begin_forward(self._mask_override, rng=self._draw(plan))
                 plan.run("f3d")
                 cq = self.num_features // t
                 y = plan.out3d.tensor.view(b, t, h, w, cq)
@@ -539,7 +570,7 @@ class MultiDimStacker(nn.Module):
             t = self.num_stacks
             cq = f // t
             plan.yq.tensor.view(b, t, h, w, cq).copy_(x.detach().view(b, t, cq, h, w).permute(0, 1, 3, 4, 2))
-            plan.begin_forward(self._mask_override)
+            plan.begin_forward(self._mask_override, rng=self._draw(plan))
             plan.run("fhead")
             return plan.logits.tensor.view(b, -1).clone()
 

@@ -174,4 +174,5 @@ def data_parallel(module, group=None, broadcast: bool = True, force_collective: 
     if broadcast:
         broadcast_state(module, 0, group)
     module._grad_sync = BucketedSync(group, force_collective) if bucketed else (lambda flat: allreduce_mean_(flat, group, force_collective))
+    module.rng_stream = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0      # device_rng: same seed, own masks per rank
     return module

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 136
+#define MDS_VERSION 137
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -116,6 +116,33 @@ typedef struct {
   long slot_stride;
 } mds_wgrad_finish_args;
 long mds_wgrad_finish(const mds_wgrad_finish_args* a, mds_stream_t stream);
+
+/* ---- DropPath / dropout masks from a counter-based generator that the engine owns (MultiDimStacker.device_rng): one launch
+ * fills the plan's whole fp32 mask arena.  Element e of the arena (0 <= e < n) is, exactly:
+ *     counter = (e >> 2, stream, draw & 0xffffffff, draw >> 32)          four 32-bit words
+ *     key     = (seed & 0xffffffff, seed >> 32)                          two 32-bit words
+ *     r       = word (e & 3) of Philox4x32-10(counter, key)
+ *     u       = (r >> 8) * 2^-24                                          (24 bits: exact in fp32, 0 <= u < 1)
+ *     mask[e] = u < keep[e] ? 1.0f / keep[e] : 0.0f                       (IEEE fp32 division; keep[e] == 1 gives 1.0 always)
+ * Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 definition): ten times
+ *     (c0, c1, c2, c3) <- (hi(M1 * c2) ^ c1 ^ k0,  lo(M1 * c2),  hi(M0 * c0) ^ c3 ^ k1,  lo(M0 * c0))
+ * with M0 = 0xD2511F53, M1 = 0xCD9E8D57, hi / lo the halves of the 64-bit product, and between two rounds (nine times)
+ * (k0, k1) <- (k0 + 0x9E3779B9, k1 + 0xBB67AE85), all mod 2^32.  The same (seed, stream, draw, e) gives the same bit on every
+ * device, in the test simulator and in a host implementation of these lines; no state lives in the library.
+ * mask and keep are 16-byte aligned, 0 < n < 2^31, every keep[e] in (0, 1].  `keep` is device memory: with keep_checked == 0
+ * the entry point reads it back (one blocking copy of n floats on `stream`) and refuses a value outside (0, 1]; a caller that
+ * has checked its table once (the planner builds it on the host) sets keep_checked = 1 and the call is one asynchronous
+ * launch.  Like the other entry points added since version 136 it returns `long`: 0, or a negative MDS_ERR_* code.          */
+typedef struct {
+  float* mask;         /* [n] out */
+  const float* keep;   /* [n] keep probability per element */
+  long n;
+  unsigned long long seed;
+  unsigned long long draw;
+  unsigned int stream;
+  int keep_checked;    /* nonzero: the caller vouches for the range of keep[] - no read-back */
+} mds_mask_fill_args;
+long mds_mask_fill(const mds_mask_fill_args* a, mds_stream_t stream);
 
 /* ---- output transform ("epilogue") for plans that KNOW the BatchNorm statistics before the producer runs (eval mode /
  * the predictor): the producer stores act(acc*scale[c] + shift[c]) instead of the raw convolution output, so no consumer

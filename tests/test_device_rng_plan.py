@@ -1,0 +1,274 @@
+"""MultiDimStacker.device_rng through the planner and the module, on the host kernel simulator: the DropPath / dropout masks
+of a training forward are the host-predictable function of (seed, stream, draw) that include/mds.h defines, torch's generator
+is not touched, and the draw counter counts drawing forwards - whatever plan runs them."""
+import copy
+import os
+import pickle
+import subprocess
+import sys
+import textwrap
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import multidim_stacker_ref as orc
+import mds
+from conftest import ROOT
+from test_module_emu import _pair, _cmp
+import device_rng_host as host
+from device_rng_host import feed_oracle
+
+KW = dict(orc.BASIC_CONFIG_KWARGS, drop_rate=0.2, drop_path_rate=0.2)
+PATHS = [ROOT, os.path.join(ROOT, "ball-action-spotting_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]
+
+
+def _step(model, x, tgt):
+    model.zero_grad(set_to_none=True)
+    out = model(x)
+    orc.sigmoid_focal_loss(out, tgt, alpha=-1.0, gamma=1.2).backward()
+    return out.detach().clone()
+
+
+def _plans(prod, **want):
+    return [pl for pool in prod._cache.plans.values() for pl in pool if all(getattr(pl, k) == v for k, v in want.items())]
+
+
+X = lambda seed=1, h=64, w=64: torch.rand(1, 15, h, w, generator=torch.Generator().manual_seed(seed))
+TGT = torch.tensor([[1.0, 0.0]])
+
+
+def test_the_mask_arena_is_the_host_prediction():
+    _, prod = _pair(KW)
+    prod.train()
+    prod.device_rng = True
+    prod.seed_rng((9 << 32) + 5)
+    x = X(h=32, w=32)
+    for draw in range(2):
+        _step(prod, x, TGT)
+        (plan,) = _plans(prod, kind="full", need_grad=True)
+        assert plan.device_rng and plan.masks
+        assert torch.equal(plan.mask_arena.tensor, host.mask(host.plan_keep(plan), (9 << 32) + 5, 0, draw)), draw
+        assert prod.rng_draws == draw + 1
+    assert prod.rng_state() == dict(seed=(9 << 32) + 5, stream=0, draws=2)
+    prod.rng_stream = 3
+    _step(prod, x, TGT)
+    assert torch.equal(plan.mask_arena.tensor, host.mask(host.plan_keep(plan), (9 << 32) + 5, 3, 2))
+
+
+def test_train_step_with_drop_rates_fp32_vs_oracle_fed_the_predicted_masks():
+    """the test the feature exists for: a step with drop_rate = drop_path_rate = 0.2 against the oracle, whose masks are computed on
+    the host from (seed, stream, draw) and the oracle's own drop probabilities - nothing is read back from the engine.  Bars of
+    test_module_emu.test_full_model_train_step_fp32_vs_oracle (logits and buffers 1e-4, gradients 2e-3)."""
+    ref, prod = _pair(KW)
+    ref.train(); prod.train()
+    assert hasattr(prod, "seed_rng"), "MultiDimStacker has no device-side mask stream"
+    prod.device_rng = True
+    prod.seed_rng(20261017)
+    x = X()
+    for draw in range(2):                                   # the second step draws other masks: draw number 1
+        arena = feed_oracle(ref, 1, 20261017, 0, draw)
+        assert 0 < int((arena == 0).sum()) < arena.numel()       # something is dropped, something is kept
+        lr = _step(ref, x, TGT)
+        lp = _step(prod, x, TGT)
+        _cmp("logits", lp, lr, 1e-4, 1e-4)
+        rp, pp = dict(ref.named_parameters()), dict(prod.named_parameters())
+        floor = 1e-2 * float(np.median([p.grad.abs().max().item() for p in rp.values()]))
+        worst = sorted((((pp[n].grad - rp[n].grad).abs().max().item() / max(rp[n].grad.abs().max().item(), floor)), n) for n in rp)[::-1]
+        print(f"[device rng emu] draw {draw}: worst relative gradient errors {worst[:3]}")
+        assert worst[0][0] < 2e-3, f"worst relative grad errors: {worst[:8]}"
+        for (n, b), (_, b2) in zip(ref.named_buffers(), prod.named_buffers()):
+            _cmp("buffer " + n, b2, b, 1e-4, 1e-4)
+
+
+def test_torch_generator_is_untouched_with_the_switch_on_and_advances_with_it_off():
+    _, prod = _pair(KW)
+    prod.train()
+    x = X(h=32, w=32)
+    before = torch.get_rng_state()
+    _step(prod, x, TGT)                                     # the default plan: bernoulli_ on torch's generator
+    assert not torch.equal(torch.get_rng_state(), before)
+    assert prod.rng_draws == 0 and prod.rng_seed is None
+    prod.device_rng = True
+    torch.manual_seed(1234)
+    before = torch.get_rng_state()
+    _step(prod, x, TGT)
+    assert torch.equal(torch.get_rng_state(), before)
+    assert prod.rng_draws == 1 and prod.rng_seed == 1234    # torch.manual_seed governs a run that never calls seed_rng()
+    torch.manual_seed(99)
+    _step(prod, x, TGT)
+    assert prod.rng_seed == 1234 and prod.rng_draws == 2    # fixed after the first drawing forward
+    prod.seed_rng(5)
+    assert prod.rng_state() == dict(seed=5, stream=0, draws=0)
+
+
+def test_counter_semantics():
+    _, a = _pair(KW)
+    _, b = _pair(KW)
+    a.train(); b.train()
+    a.device_rng = b.device_rng = True
+    a.seed_rng(31); b.seed_rng(31)
+    x, y = X(h=32, w=32), X(2, h=32, w=64)
+    # same seed: the same logits, step by step; another draw: other masks
+    la = [_step(a, x, TGT) for _ in range(3)]
+    state1 = None
+    lb = []
+    for i in range(3):
+        lb.append(_step(b, x, TGT))
+        if i == 0:
+            state1 = b.rng_state()
+    assert all(torch.equal(p, q) for p, q in zip(la, lb))
+    assert not torch.equal(la[0], la[1]) and not torch.equal(la[1], la[2])
+    # rng_state taken after step 1 replays steps 2 and 3 bit for bit
+    assert state1 == dict(seed=31, stream=0, draws=1)
+    b.set_rng_state(b.rng_state())
+    assert b.rng_draws == 3
+    b.set_rng_state(state1)
+    assert torch.equal(_step(b, x, TGT), la[1]) and torch.equal(_step(b, x, TGT), la[2])
+    # forwards of another shape in between (other plans; the cache is cleared too): draw number d still gets the masks of d
+    b.seed_rng(31)
+    assert torch.equal(_step(b, x, TGT), la[0])
+    _step(b, y, TGT)                                        # draw 1 goes to the other shape
+    (py,) = _plans(b, kind="full", need_grad=True, W=64)
+    assert torch.equal(py.mask_arena.tensor, host.mask(host.plan_keep(py), 31, 0, 1))
+    b.clear_plans()
+    assert torch.equal(_step(b, x, TGT), la[2])             # draw 2 on a freshly built plan
+    assert b.rng_draws == 3
+    # eval forwards never draw
+    b.eval()
+    with torch.no_grad():
+        b(x)
+    assert b.rng_draws == 3
+    # a model without stochastic layers has no mask arena: nothing to draw
+    _, c = _pair(dict(KW, drop_rate=0.0, drop_path_rate=0.0))
+    c.train()
+    c.device_rng = True
+    _step(c, x, TGT)
+    assert c.rng_draws == 0 and c.rng_seed is None and not any(pl.device_rng for pl in _plans(c))
+
+
+def test_switch_and_stream_state_are_engine_state():
+    m = mds.MultiDimStacker(**KW)
+    assert m.device_rng is False and m.rng_seed is None and m.rng_stream == 0 and m.rng_draws == 0
+    keys = list(m.state_dict())
+    m.device_rng = True
+    m.set_rng_state(dict(seed=(1 << 40) + 3, stream=2, draws=17))
+    assert list(m.state_dict()) == keys and len(keys) == 515
+    for c in (copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
+        assert c.device_rng is True and c.rng_state() == dict(seed=(1 << 40) + 3, stream=2, draws=17)
+    old = copy.deepcopy(m)
+    for k in ("device_rng", "rng_seed", "rng_stream", "rng_draws"):      # a module pickled before the attributes existed: off
+        del old.__dict__[k]
+    from hipemu.loader import load_emulator
+    old._lib = load_emulator()
+    assert not old.train()._plan(torch.rand(1, 15, 32, 32), "full", 1, 15, 32, 32, True).device_rng
+    assert old.rng_state() == dict(seed=None, stream=0, draws=0)
+
+
+def test_sub_forwards_draw_once_per_drawing_call():
+    _, prod = _pair(KW)
+    prod.train()
+    prod.device_rng = True
+    prod.seed_rng(8)
+    g = torch.Generator().manual_seed(2)
+    S, C3, F = prod.num_stacks, prod.num_3d_features, prod.num_features
+    calls = [("2d", prod.forward_2d, torch.rand(1, 15, 32, 32, generator=g)), ("3d", prod.forward_3d, torch.rand(1, S, C3, 2, 2, generator=g)),
+             ("head", prod.forward_head, torch.rand(1, F, 2, 2, generator=g)), ("tail", prod.forward_tail, torch.rand(1, S, C3, 2, 2, generator=g))]
+    draw = 0
+    for kind, fwd, inp in calls:
+        for grad in ((True,) if kind == "tail" else (True, False)):
+            with torch.enable_grad() if grad else torch.no_grad():
+                fwd(inp)
+            (plan,) = _plans(prod, kind=kind, need_grad=grad)
+            assert plan.device_rng and prod.rng_draws == draw + 1, (kind, grad, prod.rng_draws)
+            assert torch.equal(plan.mask_arena.tensor, host.mask(host.plan_keep(plan), 8, 0, draw)), (kind, grad)
+            draw += 1
+    prod.eval()
+    with torch.no_grad():
+        prod.forward_head(prod.forward_3d(prod.forward_2d(calls[0][2])))
+    assert prod.rng_draws == draw
+
+
+def test_compiled_training_forward_traces_and_draws():
+    import torch._dynamo as dynamo
+    _, prod = _pair(KW)
+    prod.train()
+    prod.device_rng = True
+    prod.seed_rng(13)
+    x = X(h=32, w=32)
+    eager = [_step(prod, x, TGT) for _ in range(2)]
+    prod.seed_rng(13)
+    dynamo.reset()
+    cm = torch.compile(prod, fullgraph=True, backend="aot_eager")
+    assert torch.equal(_step(cm, x, TGT), eager[0]) and torch.equal(_step(cm, x, TGT), eager[1])
+    assert prod.rng_draws == 2
+
+
+CHILD = """
+import sys
+sys.path[:0] = {paths!r}
+import torch
+from oracle import multidim_stacker_ref as orc
+from test_module_emu import _pair
+import mds.module, device_rng_host as host
+assert not mds.module.USE_CUSTOM_OP
+_, prod = _pair(dict(orc.BASIC_CONFIG_KWARGS, drop_rate=0.2, drop_path_rate=0.2))
+prod.train()
+prod.device_rng = True
+prod.seed_rng(21)
+x = torch.rand(1, 15, 32, 32, generator=torch.Generator().manual_seed(1))
+for draw, grad in enumerate((True, False, True)):
+    with torch.enable_grad() if grad else torch.no_grad():
+        out = prod(x)
+    if grad:
+        out.sum().backward()
+    (plan,) = [pl for pool in prod._cache.plans.values() for pl in pool if pl.need_grad == grad]
+    assert prod.rng_draws == draw + 1, prod.rng_draws
+    assert torch.equal(plan.mask_arena.tensor, host.mask(host.plan_keep(plan), 21, 0, draw)), draw
+print("CHILD OK")
+"""
+
+
+def test_the_untraced_path_draws_once_per_call(tmp_path):
+    """MDS_CUSTOM_OP=0 (read at import: a child process): _MDSFunction and the no-grad training forward"""
+    script = tmp_path / "child.py"
+    script.write_text(textwrap.dedent(CHILD.format(paths=PATHS)))
+    r = subprocess.run([sys.executable, str(script)], env=dict(os.environ, MDS_CUSTOM_OP="0"), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "CHILD OK" in r.stdout, r.stderr[-3000:]
+
+
+def _dp_worker(rank, world, port, tmp, paths):
+    sys.path[:0] = [p for p in paths if p not in sys.path]
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(2)
+    from mds import parallel as par
+    _, prod = _pair(KW)
+    par.data_parallel(prod)
+    assert prod.rng_stream == rank
+    prod.train()
+    prod.device_rng = True
+    prod.seed_rng(77)                                       # every rank: the same seed
+    _step(prod, X(h=32, w=32), TGT)
+    (plan,) = _plans(prod, kind="full", need_grad=True)
+    assert torch.equal(plan.mask_arena.tensor, host.mask(host.plan_keep(plan), 77, rank, 0))
+    torch.save(plan.mask_arena.tensor.clone(), os.path.join(tmp, f"m{rank}.pt"))
+    dist.barrier()
+    if rank == 0:
+        other = torch.load(os.path.join(tmp, "m1.pt"))
+        assert other.shape == plan.mask_arena.tensor.shape and not torch.equal(other, plan.mask_arena.tensor)
+    dist.destroy_process_group()
+
+
+def test_data_parallel_ranks_draw_from_their_own_stream(tmp_path):
+    import socket
+    import torch.multiprocessing as mp
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, str(tmp_path), PATHS)) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(900)
+        assert p.exitcode == 0
