@@ -19,13 +19,13 @@ Reference mapping: forward_2d / forward_3d / forward_head of
 from __future__ import annotations
 
 import contextlib
-import os
 import ctypes as C
 from typing import Dict, List, Optional
 
 import torch
 
 from . import cabi, geometry as geo
+from .options import DevSwitches, PlanOptions
 from .cabi import MDS_STAT_SLOTS as SLOTS
 
 PRO_NONE, PRO_AFFINE, PRO_BN_SILU, PRO_BN_GATE, PRO_GATE = 0, 1, 2, 3, 4
@@ -203,8 +203,8 @@ def _hip_path():
 class Plan:
     """The recorded schedules + buffers for one configuration."""
 
-    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, eval_fusion=False,
-                 eval_se_fusion=False, eval_er_fusion=False, deterministic=False, device_rng=False):
+    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, options=PlanOptions()):
+        self.dev = DevSwitches.from_env()      # read here, never later: building and running this plan consult only this record
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
                                     # tail plans: ("probs", tta) - the head also writes the TTA-mean of the sigmoids (mds.predict)
@@ -224,27 +224,27 @@ class Plan:
         # fp32 plans (speed is not their point, the 1e-3 parity bar is): the sums of the residual-stream BatchNorms - sum g cancels
         # to ~1e-3 of its absolute mass over 1.2 - 5.9 M rows - always go through mds_bn_bwd_reduce, whose fp32 instantiation
         # accumulates per thread and per block in fp64 (fp32 block partials put the worst batch-4 bias at 1.2 - 1.5e-3).
-        self.fuse_bn_bwd = os.environ.get("MDS_FUSE_BN_BWD", "1") != "0" and code == cabi.MDS_BF16
+        self.fuse_bn_bwd = self.dev.fuse_bn_bwd and code == cabi.MDS_BF16
         # inference plans (eval-mode BatchNorm, no gradient): producers store activated outputs (mds_epi_t)
-        self.eval_epilogues = (not training) and (not need_grad) and os.environ.get("MDS_EVAL_EPI", "1") == "1"
+        self.eval_epilogues = (not training) and (not need_grad) and self.dev.eval_epi
         # MultiDimStacker.eval_fusion: the 2D inverted-residual blocks of an inference plan expand their input inside the
         # depthwise launch (mds_expand_t) - no mid-wide y1 tensor, no expansion pw_fwd
-        self.eval_fusion = bool(eval_fusion) and self.eval_epilogues
+        self.eval_fusion = options.eval_fusion and self.eval_epilogues
         # MultiDimStacker.eval_se_fusion: the pooling depthwise launch of an inference plan also computes the squeeze-excite
         # gate (mds_se_tail_t) - no se_fc_fwd launch between the depthwise and the gated projection
-        self.eval_se_fusion = bool(eval_se_fusion) and self.eval_epilogues
+        self.eval_se_fusion = options.eval_se_fusion and self.eval_epilogues
         # MultiDimStacker.eval_er_fusion: the edge-residual blocks of an inference plan run their 3x3 expansion and their 1x1
         # projection in one launch (mds_project_t) - no mid-wide ya tensor, no projection pw_fwd
-        self.eval_er_fusion = bool(eval_er_fusion) and self.eval_epilogues
+        self.eval_er_fusion = options.eval_er_fusion and self.eval_epilogues
         # MultiDimStacker.deterministic: every launch of the backward schedule that ends in fp32 atomics on a parameter gradient takes
         # the fixed-order way out (mds_partial_t): slots in a workspace + the finishing kernel, issued by the same entry point on the
         # same stream - so the finish is on the producer's stream, before the gradient-bucket cut and join_backward, by construction.
         # Plans without a backward schedule have no such launch: they ignore the switch.
-        self.deterministic = bool(deterministic) and need_grad
-        self.det_workspace_bytes = 0
+        self.deterministic = options.deterministic and need_grad
         # MultiDimStacker.device_rng: begin_forward fills the mask arena with one mds_mask_fill launch from the (seed, stream, draw)
         # the module hands it, instead of two launches on torch's generator.  Plans without masks ignore the switch (set in _finalize).
-        self.device_rng = bool(device_rng) and training
+        self.device_rng = options.device_rng and training
+        self.det_workspace_bytes = 0
         self.in_flight = False
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
@@ -254,7 +254,7 @@ class Plan:
         self._recs: Dict[str, list] = {"2d": [], "3d": [], "head": []}
         self.pack_jobs = []
         self._se_pending = []       # squeeze-excite parameter-gradient launches deferred to the end of their gradient bucket
-        self.se_table = os.environ.get("MDS_SE_PARAMS_TABLE", "1") == "1"
+        self.se_table = self.dev.se_params_table
         self._bn_buffers = []    # running_mean / running_var / num_batches_tracked of every BatchNorm this plan updates
         self.taps = []           # block outputs in forward order: dict(tag, buf, bn (raw tensor read through BN+SiLU) or None, rows, C)
         self.masks = []          # (Lazy view, keep_prob)
@@ -470,8 +470,8 @@ class Plan:
                       y=dxb, pro=dict(mode=0), residual=residual, stats=None)
         fused = None
         if (head is not None and (head["mode"] != POST_MASK or head["rpg"] == IH * IW)
-                and (head["mode"] != POST_SILU or os.environ.get("MDS_FUSE_CONV_POST_SILU", "1") == "1")
-                and os.environ.get("MDS_FUSE_CONV_POST", "0") == "1"
+                and (head["mode"] != POST_SILU or self.dev.fuse_conv_post_silu)
+                and self.dev.fuse_conv_post
                 and self.lib.fn["conv_dgrad_post_ok"](int(self.code), int(N), int(IH), int(IW), int(Cin), int(Cout), int(stride), int(residual is not None))):
             common["post"] = head["bn"].post(head)
             fused = head["bn"]
@@ -540,7 +540,7 @@ class Plan:
         R = blk.se.rd
         pooled, hidden, gate = self.zero_fwd64(groups * mid), self.f32(groups * R), self.f32(groups * mid)
         # the depthwise pass stores the activation AND takes its per-image channel means (the squeeze-excite input): no se_pool launch
-        fuse_pool = groups == N and os.environ.get("MDS_EVAL_POOL", "1") == "1"
+        fuse_pool = groups == N and self.dev.eval_pool
         se = blk.se
         w2t = self.pack(se.conv_expand.weight, cabi.MDS_PACK_IO_F32, mid, R, 1)
         # ... and, with eval_se_fusion, the block that completes an image's means also computes its gate: no se_fc_fwd launch
@@ -591,7 +591,7 @@ class Plan:
         # (Rounds 2-3 had the pooling pass also WRITE silu(bn2(y2)) for them - free while that pass was bound by its atomics'
         # epilogue; with the per-channel epilogue the 2 x mid-width write + read costs more than the prologue's arithmetic:
         # 12.84 -> 12.68 ms per step, MDS_SE_ACT=1 restores it.)
-        keep_act = os.environ.get("MDS_SE_ACT", "0") == "1"
+        keep_act = self.dev.se_act
         a2 = self.act(Mout, mid) if keep_act else y2
         self.op(fseg, "se_pool", dtype=self.code, groups=groups, rows_per_group=rpg, C=mid, y=y2, scale=bn2.scale,
                 shift=bn2.shift, pooled=pooled, act=a2 if keep_act else None)
@@ -678,7 +678,7 @@ class Plan:
                 return None
             # (u0.reduced is bn0: the first 3x3 layer's data gradient stored g = u * silu'(z) and took the sums - k_c3.hip, POST_SILU)
             g0 = gsrc(G_PLAIN, u0.buf) if u0.reduced is bn0 else gsrc(G_SILU, u0.buf)
-            if self.tdt == torch.bfloat16 and os.environ.get("MDS_STEM_DYP", "1") == "1":
+            if self.tdt == torch.bfloat16 and self.dev.stem_dyp:
                 # the stem has no data gradient: its BatchNorm-backward apply pass would only feed the weight gradient, which
                 # forms dy = A*u*silu'(z) + B*y + D on load instead (no 0.9 GB apply launch at the very end of the step)
                 if u0.reduced is not bn0:
@@ -1105,28 +1105,25 @@ class Plan:
     class _ExtEvents:
         """hipEvent_t handles used as kernel STOP events (hipExtLaunchKernelGGL through mds_launch_event) + hipStreamWaitEvent"""
 
-        def __init__(self, device):
-            import ctypes
-            self.ct = ctypes
-            self.hip = ctypes.CDLL(_hip_path())
-            self.hip.hipEventCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
-            self.hip.hipStreamWaitEvent.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
-            self.device, self.ev = device, {}
+        def __init__(self, device, flags):
+            self.hip = C.CDLL(_hip_path())
+            self.hip.hipEventCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+            self.hip.hipStreamWaitEvent.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
+            self.device, self.ev, self.flags = device, {}, flags
             # hipEventDisableTiming | hipEventDisableSystemFence: these events only order the second stream behind a kernel of
             # the chain - nobody on the host inspects them, so the system-scope fence (cache write-back for the host's benefit)
             # a default event adds when it completes is dropped; the kernel's own device-scope release and the waiting stream's
             # acquire stay.  12.67 -> 12.56 ms per step same-box (profiles/r05_ab_event_flags.txt; MDS_EVENT_FLAGS=0 = default events).
-            self.flags = int(os.environ.get("MDS_EVENT_FLAGS", "0x20000002"), 0)
 
         def _create(self):
             """one hipEvent_t with the cheapest flags this runtime accepts: disable-timing | disable-system-fence (ROCm >= 6.x), then
             disable-timing alone, then a default event - the first combination that works is remembered (a runtime that
             rejects the fence flag must not fail the first backward)"""
-            v = self.ct.c_void_p()
+            v = C.c_void_p()
             tried = []
             for flags in dict.fromkeys((self.flags, 0x2, 0x0)):
                 with torch.cuda.device(self.device):
-                    rc = self.hip.hipEventCreateWithFlags(self.ct.byref(v), flags)
+                    rc = self.hip.hipEventCreateWithFlags(C.byref(v), flags)
                 if rc == 0 and v.value:
                     self.flags = flags
                     return v.value
@@ -1145,10 +1142,10 @@ class Plan:
                 raise RuntimeError(f"hipStreamWaitEvent failed: {rc}")
 
     def _ext_events(self):
-        if os.environ.get("MDS_SIDE_EVENTS", "stop") != "stop":
+        if not self.dev.stop_events:
             return None
         if getattr(self, "_ext", None) is None:
-            self._ext = Plan._ExtEvents(self.device)
+            self._ext = Plan._ExtEvents(self.device, self.dev.event_flags)
         return self._ext
 
     def join_backward(self):
@@ -1157,7 +1154,7 @@ class Plan:
             torch.cuda.current_stream(self.device).wait_stream(self._side)
 
     def _side_stream(self):
-        if self.device.type != "cuda" or os.environ.get("MDS_SIDE_STREAM", "1") == "0":
+        if self.device.type != "cuda" or not self.dev.side_stream:
             return None
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -1247,13 +1244,12 @@ class Plan:
 
     def _memset(self, t):
         """zero a uint8 arena on the current stream: hipMemsetAsync (one runtime fill, also a node of a captured hipGraph)"""
-        if t.device.type != "cuda" or os.environ.get("MDS_MEMSET", "hip") != "hip":
+        if t.device.type != "cuda" or not self.dev.hip_memset:
             t.zero_()
             return
         if Plan._hip is None:
-            import ctypes
-            Plan._hip = ctypes.CDLL(_hip_path())
-            Plan._hip.hipMemsetAsync.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p]
+            Plan._hip = C.CDLL(_hip_path())
+            Plan._hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         rc = Plan._hip.hipMemsetAsync(t.data_ptr(), 0, t.numel() * t.element_size(), self._stream())
         if rc != 0:
             raise RuntimeError(f"hipMemsetAsync failed: {rc}")

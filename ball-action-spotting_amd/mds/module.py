@@ -28,7 +28,7 @@ import torch
 from torch import nn
 
 from . import cabi
-from .engine import Plan
+from .engine import Plan, PlanOptions
 from .structure import (EncoderP, InvertedResidual3dP, GeneralizedMeanPoolingP, TAIL_BN_EPS)
 
 MAX_PLANS = 8     # launch plans kept per module (LRU); each pins its activation arena (12 GB at config 2)
@@ -469,12 +469,8 @@ class MultiDimStacker(nn.Module):
         lib = self._library(x)
         enc_grad = any(p.requires_grad for p in self.conv2d_encoder.parameters())
         code = self._code() if code is None else code
-        fusion = bool(getattr(self, "eval_fusion", False))     # (a module unpickled from before the attribute existed: off)
-        se_fusion = bool(getattr(self, "eval_se_fusion", False))
-        er_fusion = bool(getattr(self, "eval_er_fusion", False))
-        det = bool(getattr(self, "deterministic", False)) and need_grad      # (plans without a backward schedule ignore the switch)
-        dev_rng = bool(getattr(self, "device_rng", False)) and self.training     # (eval plans have no masks)
-        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, fusion, se_fusion, er_fusion, det, dev_rng)
+        opts = PlanOptions.of(self, self.training, need_grad)
+        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, opts)
         cache = self._cache
         pool = cache.plans.setdefault(key, [])
         cache.plans.move_to_end(key)
@@ -482,8 +478,7 @@ class MultiDimStacker(nn.Module):
             if not plan.in_flight and not plan.stale():
                 return plan
         pool[:] = [p for p in pool if not p.stale()]
-        plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, eval_fusion=fusion,
-                    eval_se_fusion=se_fusion, eval_er_fusion=er_fusion, deterministic=det, device_rng=dev_rng)
+        plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, options=opts)
         pool.append(plan)
         cache.evict(key)
         return plan

@@ -27,11 +27,26 @@ The module's weights are read in place (the same ``mds.MultiDimStacker`` instanc
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
 
 from . import cabi
+
+
+@contextlib.contextmanager
+def _overridden(obj, values):
+    """set the non-None `values` on obj for the body, then put back exactly those; one that did not exist before is removed again"""
+    absent = object()
+    saved = {k: getattr(obj, k, absent) for k, v in values.items() if v is not None}
+    try:
+        for k in saved:
+            setattr(obj, k, values[k])
+        yield
+    finally:
+        for k, v in saved.items():
+            delattr(obj, k) if v is absent else setattr(obj, k, v)
 
 
 class StackIndexes:
@@ -167,35 +182,23 @@ class StreamPredictor:
             return c
         h, w, dev = self._built
         m, b = self.m, (2 if self.tta else 1)
-        saved, saved_fusion = m.compute_dtype, getattr(m, "eval_fusion", False)
-        saved_se = getattr(m, "eval_se_fusion", False)
-        saved_er = getattr(m, "eval_er_fusion", False)
-        if self.compute_dtype is not None:
-            m.compute_dtype = self.compute_dtype
-        if self.eval_fusion is not None:
-            m.eval_fusion = bool(self.eval_fusion)
-        if self.eval_se_fusion is not None:
-            m.eval_se_fusion = bool(self.eval_se_fusion)
-        if self.eval_er_fusion is not None:
-            m.eval_er_fusion = bool(self.eval_er_fusion)
-        try:
-            with torch.no_grad():
-                probe = self.frames[0]
-                if c is None:
-                    c = self.plans[n] = dict(p2d=[], ptail=[], graphs={}, warm={}, ver={}, cache={}, w={})
-                while len(c["p2d"]) < lanes:       # a plan that is in flight is never handed out again: every call builds (or finds) another
-                    p2d = m._plan(probe, "2d", n * b, self.ss, self.H, self.W, False, ingest=(h, w, n))
-                    p2d.in_flight = True           # owned by this predictor
-                    c["w"]["2d", len(c["p2d"])] = p2d.weight_tensors()
-                    c["p2d"].append(p2d)
-                while len(c["ptail"]) < (tails or 1):
-                    p2d = c["p2d"][0]
-                    pt = m._plan(probe, "tail", n * b, self.S * self.ss, p2d.h, p2d.w, False, ingest=("probs", b))
-                    pt.in_flight = True
-                    c["w"]["tail", len(c["ptail"])] = pt.weight_tensors()
-                    c["ptail"].append(pt)
-        finally:
-            m.compute_dtype, m.eval_fusion, m.eval_se_fusion, m.eval_er_fusion = saved, saved_fusion, saved_se, saved_er
+        flags = {k: getattr(self, k) for k in ("eval_fusion", "eval_se_fusion", "eval_er_fusion")}
+        over = dict(compute_dtype=self.compute_dtype, **{k: v if v is None else bool(v) for k, v in flags.items()})
+        with _overridden(m, over), torch.no_grad():
+            probe = self.frames[0]
+            if c is None:
+                c = self.plans[n] = dict(p2d=[], ptail=[], graphs={}, warm={}, ver={}, cache={}, w={})
+            while len(c["p2d"]) < lanes:       # a plan that is in flight is never handed out again: every call builds (or finds) another
+                p2d = m._plan(probe, "2d", n * b, self.ss, self.H, self.W, False, ingest=(h, w, n))
+                p2d.in_flight = True           # owned by this predictor
+                c["w"]["2d", len(c["p2d"])] = p2d.weight_tensors()
+                c["p2d"].append(p2d)
+            while len(c["ptail"]) < (tails or 1):
+                p2d = c["p2d"][0]
+                pt = m._plan(probe, "tail", n * b, self.S * self.ss, p2d.h, p2d.w, False, ingest=("probs", b))
+                pt.in_flight = True
+                c["w"]["tail", len(c["ptail"])] = pt.weight_tensors()
+                c["ptail"].append(pt)
         p2d = c["p2d"][0]
         f = p2d.h * p2d.w * m.num_3d_features
         if self.store is None:

@@ -9,7 +9,8 @@ remaining launches keep their shapes, buffers and streams):
   base                the product step
   no_side             every weight gradient (pw_wgrad, conv_wgrad, se_fc_bwd_params) deleted: the dependent chain alone
   no_<side family>    one weight-gradient family deleted
-  one_stream          MDS_SIDE_STREAM=0: the weight gradients on the chain's stream, nothing overlaps
+  one_stream          plan.dev = dataclasses.replace(plan.dev, side_stream=False), the plan's record of MDS_SIDE_STREAM=0: the
+                      weight gradients on the chain's stream, nothing overlaps
   fwd_only            forward + loss only (no backward, no optimizer);   bwd = base - fwd_only
   chain_bwd_only      backward chain without the side ops, forward subtracted
   drop_<family>       one CHAIN family deleted (forward and backward uses), with and without the side stream running
@@ -20,6 +21,7 @@ the column is left empty),  "1 us saved here = x us of step" = d_step / in-step 
 """
 import argparse
 import csv
+import dataclasses
 import os
 import re
 import sys
@@ -138,10 +140,13 @@ def main():
         record("no_side", with_deleted(set(SIDE_FAMILIES), timed), SIDE_FAMILIES)
         for f in SIDE_FAMILIES:
             record(f"no_{f}", with_deleted({f}, timed), [f])
-        os.environ["MDS_SIDE_STREAM"] = "0"
+        two_streams = plan.dev       # the switches are read at plan build: the live plan's record is replaced, not the environment
+        plan.dev = dataclasses.replace(plan.dev, side_stream=False)
+        assert plan._side_stream() is None
         record("one_stream", timed())
         record("one_stream_no_side", with_deleted(set(SIDE_FAMILIES), timed), SIDE_FAMILIES)
-        os.environ["MDS_SIDE_STREAM"] = "1"
+        plan.dev = two_streams
+        assert plan._side_stream() is not None
         fwd = timed(backward=False)
         record("fwd_only", fwd)
         record("chain_bwd_only(no_side - fwd)", rows[1][1] - fwd)
