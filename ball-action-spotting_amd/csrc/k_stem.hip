@@ -555,3 +555,181 @@ extern "C" int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream)
   if (int rc = mds_check_launch("stem_wgrad")) return rc;
   return wg_finish(a->partial, a->dw, (long)a->Cout * 27, sg.slots, stream);
 }
+
+// ---- data gradient: dx[n][p][iy][ix] = sum_{ky,kx} sum_o w[o][p][ky][kx] * dy[n][(iy + pad_t - ky) / 2][(ix + pad_l - kx) / 2][o] over the
+// taps whose two divisions are exact and land inside dy - the transposed stride-2 convolution, 32 -> 3, written as a GATHER: no
+// atomics, every dx element stored once.  In a = iy + pad_t, b = ix + pad_l the parity decides the taps: an even a takes ky = 0
+// (dy row a/2) and ky = 2 (row a/2 - 1), an odd a takes ky = 1 (row (a-1)/2); columns alike.  So the 2 x 2 patch (2A..2A+1, 2B..2B+1)
+// reads dy rows A-1, A and columns B-1, B, and every filter value is used exactly once per patch: 864 FMAs for 12 outputs.
+// A thread owns 2 rows x 4 columns x 3 planes (two patches side by side: one 16-byte store per plane and row); a block of
+// SdCfg::rows x 32 threads stages its (rows + 1) x 65 dy pixels ONCE into LDS - zeros outside dy, so the edge rules need no
+// branch in the arithmetic - in the storage type (a dy formed on load, A*g + B*y + D, is rounded to it: what mds_bn_bwd_apply would
+// have written).  In a tile row the even dy columns come first, then the odd ones: neighbouring lanes then read neighbouring LDS
+// pixels (pitch 80 B / 144 B: the sixteen lanes of a ds_read_b128 group hit sixteen different 16-byte bank groups).  The filter is
+// read through the scalar cache (wave-uniform index), an FMA takes it as its scalar operand.  Streaming: 64 B in and 48 B out per
+// patch against 864 FMAs.  Order of the sum of one element: o ascending, inside one o ky ascending, then kx - fixed, so two runs
+// give the same bits.
+#define SD_COLS 32
+template <typename T> struct SdCfg;
+template <> struct SdCfg<bf16_t> { static const int rows = 8, pitch = 40; };
+template <> struct SdCfg<float> { static const int rows = 4, pitch = 36; };
+template <typename T> MDS_DEV float stem_w(const T* w, int idx);      // w[idx] of the MDS_PACK_STEM filter, idx wave-uniform
+template <> MDS_DEV float stem_w<float>(const float* w, int idx) { return ld_uniform(w, idx); }
+template <> MDS_DEV float stem_w<bf16_t>(const bf16_t* w, int idx) {
+  const uint32_t pair = f2bits(ld_uniform((const float*)w, idx >> 1));
+  return bits2f((idx & 1) ? (pair & 0xffff0000u) : (pair << 16));
+}
+
+template <typename T, bool DYP>
+__global__ __launch_bounds__(SdCfg<T>::rows * SD_COLS) void stem_dgrad_kernel(mds_stem_dgrad_args a, int tiles_a, int tiles_b, int vec) {
+  MDS_CHAIN_PRIO();
+  constexpr int TR = SdCfg<T>::rows, NT = TR * SD_COLS, PITCH = SdCfg<T>::pitch;
+  constexpr int NC = 2 * SD_COLS + 1, NE = SD_COLS + 1;      // dy columns of a tile, the even ones of them
+  constexpr int NPX = (TR + 1) * NC;
+  constexpr int BATCH = 4;                                   // 16-byte loads a thread keeps in flight (twice that with DYP)
+  __shared__ __attribute__((aligned(16))) T dys[NPX * PITCH];
+  const int tid = threadIdx.x;
+  const int csh = a.Cout == 32 ? 2 : 1, ch = tid & ((1 << csh) - 1);      // 8-channel chunks per pixel = 1 << csh; this thread's chunk
+  const long t = xcd_contiguous(blockIdx.x, gridDim.x);     // neighbouring tiles share a halo row / column: same XCD, same L2
+  const int img = (int)(t / (tiles_a * tiles_b));
+  const int rem = (int)(t - (long)img * tiles_a * tiles_b);
+  const int A0 = (rem / tiles_b) * TR, J0 = (rem % tiles_b) * SD_COLS;
+  const int oy0 = A0 - 1, ox0 = 2 * J0 - 1;                  // dy pixel of tile position (0, 0)
+  const T* src = (const T*)(DYP ? a.dyp.g.u : a.dy);
+  const T* ysrc = (const T*)a.dyp.y;                         // the BatchNorm input y has u's layout
+  float cA[8], cB[8], cD[8], csc[8], cshf[8];
+  if (DYP) {
+    const int c = 8 * ch, C = a.Cout;
+    load8f(a.dyp.lin + c, cA); load8f(a.dyp.lin + C + c, cB); load8f(a.dyp.lin + 2 * C + c, cD);
+    load8f(a.dyp.bn + c, csc); load8f(a.dyp.bn + C + c, cshf);
+  }
+  const bool gsilu = DYP && a.dyp.g.mode == MDS_G_SILU;
+  const int nitems = NPX << csh;
+  for (int base = 0; base < nitems; base += BATCH * NT) {
+    RawV8<T> ru[BATCH], ry[DYP ? BATCH : 1];
+    unsigned ok = 0;
+#pragma unroll
+    for (int k = 0; k < BATCH; ++k) {
+      const int it = base + k * NT + tid, px = it >> csh, r = px / NC, c = px - r * NC;
+      const int oy = oy0 + r, ox = ox0 + c;
+      const bool in = it < nitems && oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW;
+      const long off = ((((long)img * a.OH + oy) * a.OW + ox) << (csh + 3)) + 8 * ch;
+      if (in) ru[k].ld(src + off);
+      else ru[k].zero();
+      if (DYP) {
+        if (in) ry[k].ld(ysrc + off);
+        else ry[k].zero();
+      }
+      ok |= (in ? 1u : 0u) << k;
+    }
+#pragma unroll
+    for (int k = 0; k < BATCH; ++k) {
+      const int it = base + k * NT + tid, px = it >> csh, r = px / NC, c = px - r * NC;
+      if (it < nitems) {
+        T* dst = dys + (r * NC + ((c & 1) ? NE + (c >> 1) : (c >> 1))) * PITCH + 8 * ch;
+        if (!DYP) {
+          ru[k].st(dst);
+        } else {
+          float u[8], yv[8], v[8];
+          ru[k].get(u);
+          ry[k].get(yv);
+          const bool in = (ok >> k) & 1u;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float g = u[e];
+            if (gsilu) g *= silu_gradf_(yv[e] * csc[e] + cshf[e]);
+            v[e] = in ? cA[e] * g + cB[e] * yv[e] + cD[e] : 0.f;      // positions outside dy contribute nothing (D != 0)
+          }
+          store8(dst, v);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int ta = tid / SD_COLS, tj = tid % SD_COLS;
+  const int iy0 = 2 * (A0 + ta) - a.pad_t, ix0 = 4 * (J0 + tj) - a.pad_l;    // first of this thread's 2 rows / 4 columns
+  if (iy0 < a.H && ix0 < a.W) {
+    const T* w = (const T*)a.w;
+    float acc[3][2][4];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int ra = 0; ra < 2; ++ra)
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb) acc[p][ra][bb] = 0.f;
+    const T* lds0 = dys + (ta * NC + tj) * PITCH;             // dy row A-1, column 2B-1 of the left patch
+    for (int oc = 0; oc < a.Cout; oc += 8) {
+      float d[2][3][8];                                        // [row A-1, A][column 2B-1, 2B, 2B+1][channel]
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const T* rowp = lds0 + r * NC * PITCH + oc;
+        load8(rowp, d[r][0]);
+        load8(rowp + NE * PITCH, d[r][1]);
+        load8(rowp + PITCH, d[r][2]);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int wb = (oc + e) * 32;
+        float wc[27];
+#pragma unroll
+        for (int k = 0; k < 27; ++k) wc[k] = stem_w<T>(w, wb + k);
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+              const float wv = wc[p * 9 + ky * 3 + kx];
+              const int ra = ky == 1 ? 1 : 0, r = ky == 2 ? 0 : 1, rb = kx == 1 ? 1 : 0;
+#pragma unroll
+              for (int q = 0; q < 2; ++q) {                    // the two patches
+                const int cc = kx == 2 ? q : q + 1;
+                acc[p][ra][2 * q + rb] = fmaf(wv, d[r][cc][e], acc[p][ra][2 * q + rb]);
+              }
+            }
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int ra = 0; ra < 2; ++ra) {
+        const int iy = iy0 + ra;
+        if (iy < 0 || iy >= a.H) continue;
+        float* row = a.dx + (((long)img * 3 + p) * a.H + iy) * a.W;
+        if (vec) {                                             // W % 4 == 0, pad_l == 0, dx 16-byte aligned: ix0 .. ix0 + 3 are inside
+          store4(row + ix0, acc[p][ra]);
+        } else {
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb)
+            if (ix0 + bb >= 0 && ix0 + bb < a.W) row[ix0 + bb] = acc[p][ra][bb];
+        }
+      }
+  }
+}
+
+extern "C" long mds_stem_dgrad(const mds_stem_dgrad_args* a, mds_stream_t stream) {
+  MDS_REQUIRE(a && a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0, "stem_dgrad: bad dims");
+  MDS_REQUIRE(a->Cout % 16 == 0 && a->Cout > 0 && a->Cout <= 32, "stem_dgrad: Cout=%d must be 16 or 32", a->Cout);
+  MDS_REQUIRE(a->pad_t >= 0 && a->pad_t <= 1 && a->pad_l >= 0 && a->pad_l <= 1, "stem_dgrad: pad_t=%d, pad_l=%d must be 0 or 1", a->pad_t, a->pad_l);
+  const bool dyp = a->dyp.mode != 0;
+  MDS_REQUIRE(a->w && (a->dy || dyp) && a->dx, "stem_dgrad: null pointer");
+  if (dyp) {
+    MDS_REQUIRE(a->dyp.mode == 1 && a->dyp.g.u && a->dyp.y && a->dyp.bn && a->dyp.lin && (a->dyp.g.mode == MDS_G_PLAIN || a->dyp.g.mode == MDS_G_SILU),
+                "stem_dgrad: dy prologue needs u, y, bn, lin and a PLAIN or SILU gradient source");
+    MDS_REQUIRE((((uintptr_t)a->dyp.g.u | (uintptr_t)a->dyp.y | (uintptr_t)a->dyp.bn | (uintptr_t)a->dyp.lin) & 15) == 0,
+                "stem_dgrad: u, y, bn and lin must be 16-byte aligned");
+  } else {
+    MDS_REQUIRE(((uintptr_t)a->dy & 15) == 0, "stem_dgrad: dy must be 16-byte aligned");
+  }
+  MDS_REQUIRE(((uintptr_t)a->w & 3) == 0 && ((uintptr_t)a->dx & 3) == 0, "stem_dgrad: w and dx must be 4-byte aligned");
+  const int vec = (a->W % 4 == 0 && a->pad_l == 0 && ((uintptr_t)a->dx & 15) == 0) ? 1 : 0;
+  const int rows = a->dtype == MDS_BF16 ? SdCfg<bf16_t>::rows : SdCfg<float>::rows;
+  const int tiles_a = cdiv(cdiv(a->H + a->pad_t, 2), rows), tiles_b = cdiv(cdiv(a->W + a->pad_l, 4), SD_COLS);
+  const long total = (long)a->N * tiles_a * tiles_b;
+  MDS_REQUIRE(total < (1L << 31), "stem_dgrad: %ld tiles", total);
+  MDS_DISPATCH_DTYPE(a->dtype, T, {
+    if (dyp) MDS_LAUNCH((stem_dgrad_kernel<T, true>), dim3((unsigned)total), dim3(SdCfg<T>::rows * SD_COLS), 0, stream, *a, tiles_a, tiles_b, vec);
+    else MDS_LAUNCH((stem_dgrad_kernel<T, false>), dim3((unsigned)total), dim3(SdCfg<T>::rows * SD_COLS), 0, stream, *a, tiles_a, tiles_b, vec);
+  });
+  return mds_check_launch("stem_dgrad");
+}

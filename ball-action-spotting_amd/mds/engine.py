@@ -161,6 +161,12 @@ def op_cost(name, kw, es):
         px = g("N") * g("OH") * g("OW")
         nwide = 2 if g("dyp") else 1      # dy formed on load (mds_dyp_t): the gradient source u AND the raw stem output y are read
         return g("N") * 3 * g("H") * g("W") * 4 + nwide * px * g("Cout") * es, 2 * 27 * g("Cout") * px
+    if name == "stem_dgrad":
+        # dx (fp32) written once, dy - or u and y, formed on load - read once; an input pixel takes 1, 2 or 4 of the 9 taps (row and
+        # column parity): 9/4 on average, i.e. 27/4 * Cout FMAs per element of dx
+        npx = g("N") * g("H") * g("W")
+        nwide = 2 if g("dyp") else 1
+        return npx * 3 * 4 + nwide * g("N") * g("OH") * g("OW") * g("Cout") * es, 2 * 27 * g("Cout") * npx // 4
     if name == "dw_fwd" and g("expand"):
         ex = g("expand")             # the narrow block input is read, the expansion computed in the launch (mds_expand_t)
         nin = g("N") * g("IH") * g("IW") * ex["cin"]
@@ -203,7 +209,8 @@ def _hip_path():
 class Plan:
     """The recorded schedules + buffers for one configuration."""
 
-    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, options=PlanOptions()):
+    def __init__(self, module, lib, device, kind, B, T, H, W, code, training, need_grad, enc_grad, ingest=None, options=PlanOptions(),
+                 input_grad=False):
         self.dev = DevSwitches.from_env()      # read here, never later: building and running this plan consult only this record
         self.lib, self.device, self.kind = lib, device, kind
         self.ingest = ingest        # 2D plans: (src_h, src_w, nsrc) - the encoder reads raw uint8 frames (pad + /255 + TTA flip fused in the stem);
@@ -216,6 +223,10 @@ class Plan:
         self.update_running = training
         self.need_grad = need_grad
         self.enc_grad = enc_grad and need_grad
+        # the caller's frame tensor requires grad: the 2D backward chain ends in mds_stem_dgrad, which writes the gradient of the
+        # (B,T,H,W) input into a buffer of the plan (self.dx).  Only where that chain exists - a frozen 2D encoder prunes it, and the
+        # module says so (MultiDimStacker._warn_no_input_grad).  Off: the schedules and buffers of a plan that never heard of it.
+        self.input_grad = bool(input_grad) and self.enc_grad and kind in ("full", "2d")
         self.m = module
         # MDS_FUSE_BN_BWD=1 (default): the data-gradient GEMM that produces a block's input gradient also takes the sums of the
         # BatchNorm backward that consumes it (mds_poststat_t): 22 bn_bwd_reduce launches less.  0: every reduce is its own launch.
@@ -364,6 +375,7 @@ class Plan:
         N = B * S
         if self.kind in ("full", "2d"):
             self.x_in = Lazy("input", B * T * H * W, torch.float32)   # bound to the caller's tensor per call
+            self.dx = self._own(B * T * H * W, torch.float32) if self.input_grad else None      # its gradient: (B*S, 3, H, W) = (B, T, H, W)
             feat, h, w = self._build_2d(N, H, W)
             self.feat, self.h, self.w = feat, h, w
         else:
@@ -673,25 +685,34 @@ class Plan:
                 x=None if self.ingest is not None else self.x_in, w=wst, y=y0, **extra)
         bn0.finalize(self, "f2d")
 
+        def stem_dgrad(seg, **dy):
+            """the gradient of the frames, after the weight gradient: the stem's dy goes to both kernels the same way (bf16: formed
+            on load by each, 2 x 602 MB read at batch 4 against 602 + 301 written + 2 x 301 read with a materialised dy0)"""
+            if self.input_grad:
+                self.op(seg, "stem_dgrad", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl, w=wst,
+                        dx=self.dx, **dy)
+
         def stem_bwd(seg, u0, nxt_head):
             if fr:
                 return None
             # (u0.reduced is bn0: the first 3x3 layer's data gradient stored g = u * silu'(z) and took the sums - k_c3.hip, POST_SILU)
             g0 = gsrc(G_PLAIN, u0.buf) if u0.reduced is bn0 else gsrc(G_SILU, u0.buf)
             if self.tdt == torch.bfloat16 and self.dev.stem_dyp:
-                # the stem has no data gradient: its BatchNorm-backward apply pass would only feed the weight gradient, which
-                # forms dy = A*u*silu'(z) + B*y + D on load instead (no 0.9 GB apply launch at the very end of the step)
+                # the stem's BatchNorm-backward apply pass would only feed the weight gradient (and, when the frames require grad, the
+                # data gradient), which form dy = A*u*silu'(z) + B*y + D on load instead (no 0.9 GB apply launch at the very end of the step)
                 if u0.reduced is not bn0:
                     bn0.bwd_reduce(self, seg, g0, y0)
                 bn0.bwd_finalize(self, seg)
                 self.op(seg, "stem_wgrad", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
                         x=self.x_in, dy=None, dw=self.grad(enc.conv_stem.weight),
                         dyp=dict(_struct="mds_dyp_t", mode=1, g=g0, y=y0, bn=bn0.buf, lin=bn0.lin))
+                stem_dgrad(seg, dy=None, dyp=dict(_struct="mds_dyp_t", mode=1, g=g0, y=y0, bn=bn0.buf, lin=bn0.lin))
                 return None
             dy0 = self.act(N * OH * OW, 32)
             bn0.backward(self, seg, g0, y0, dy0, reduce=u0.reduced is not bn0)
             self.op(seg, "stem_wgrad", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
                     x=self.x_in, dy=dy0, dw=self.grad(enc.conv_stem.weight))
+            stem_dgrad(seg, dy=dy0)
             return None
 
         stem_bwd.head = bn0.head(y0, POST_SILU)

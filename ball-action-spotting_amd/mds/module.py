@@ -13,6 +13,10 @@ the operator ``torch.ops.mds.backward``), so Dynamo / AOTAutograd / Inductor tra
 tracing compiler to add.  The operator finds its module through an integer handle (operators take tensors and scalars,
 not modules); BatchNorm's running statistics are updated by the launch as a side effect, as in eager mode.
 ``MDS_CUSTOM_OP=0`` selects the former ``torch.autograd.Function`` behind ``torch.compiler.disable`` (a graph break).
+
+``forward`` and ``forward_2d`` are differentiable in the frame tensor too: with ``x.requires_grad`` the 2D backward chain ends in the
+stem's data-gradient kernel (``mds_stem_dgrad``) and ``x.grad`` comes back in the caller's ``(B,T,H,W)`` shape.  The chain exists only
+where the 2D encoder trains; with a frozen encoder ``x.grad`` stays ``None`` and the module says so once (a ``RuntimeWarning``).
 """
 from __future__ import annotations
 
@@ -126,8 +130,9 @@ class _MDSFunction(torch.autograd.Function):
                 grads.append(flat[off:off + p.numel()].view(p.shape))
             else:
                 grads.append(None)
+        dx = _input_grad(plan, x)
         plan.in_flight = False
-        return (None, None, None, *grads)
+        return (dx, None, None, *grads)
 
 
 class _TailFunction(torch.autograd.Function):
@@ -169,7 +174,7 @@ class _TailFunction(torch.autograd.Function):
 class _SubFunction(torch.autograd.Function):
     """forward_2d / forward_3d / forward_head called on their own with autograd on (the reference's are ordinary
     differentiable methods, multidim_stacker.py:210-237): one plan of that kind with its backward schedule; gradients for
-    the input (3d, head) and for the parameters of that part of the network only."""
+    the input and for the parameters of that part of the network only."""
 
     @staticmethod
     def forward(ctx, inp, module, plan, kind, *params):
@@ -197,6 +202,7 @@ class _SubFunction(torch.autograd.Function):
                 plan.bind_input(inp)
                 plan.dfeat_in.tensor.view(b, s_, plan.h, plan.w, m.num_3d_features).copy_(dout.permute(0, 1, 3, 4, 2))
                 plan.run("b2d")
+                dinp = _input_grad(plan, inp)
             elif kind == "3d":
                 b, t, c, h, w = ctx.shape
                 cq = m.num_features // t
@@ -236,12 +242,14 @@ def _module_of(handle: int):
 # leave tagged operators alone.  tests/test_module_emu.py runs two identical calls in one compiled graph and checks that the
 # statistics advance twice.
 @torch.library.custom_op("mds::forward", mutates_args=(), tags=(torch.Tag.nondeterministic_seeded,))
-def _op_forward(x: torch.Tensor, params: List[torch.Tensor], handle: int, need_grad: bool, code: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def _op_forward(x: torch.Tensor, params: List[torch.Tensor], handle: int, need_grad: bool, code: int,
+                input_grad: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     """logits of MultiDimStacker.forward + a CPU token naming the launch plan that holds the activations for backward.
-    `params` only tells autograd what the result depends on - the kernels read the module's parameters in place."""
+    `params` only tells autograd what the result depends on - the kernels read the module's parameters in place.
+    `input_grad`: x requires grad (inside the operator autograd is off and x does not say so itself)."""
     m = _module_of(handle)
     b, t, h, w = x.shape
-    plan = m._plan(x, "full", b, t, h, w, need_grad, code=code)
+    plan = m._plan(x, "full", b, t, h, w, need_grad, code=code, input_grad=input_grad)
     token = 0
     if need_grad:
         live = m._live
@@ -259,26 +267,31 @@ def _op_forward(x: torch.Tensor, params: List[torch.Tensor], handle: int, need_g
 
 
 @_op_forward.register_fake
-def _(x, params, handle, need_grad, code):
+def _(x, params, handle, need_grad, code, input_grad):
     return x.new_empty((x.shape[0], _module_of(handle).classifier.out_features), dtype=torch.float32), torch.empty((), dtype=torch.int64)
 
 
 @torch.library.custom_op("mds::backward", mutates_args=())
-def _op_backward(dlogits: torch.Tensor, x: torch.Tensor, token: torch.Tensor, handle: int) -> torch.Tensor:
-    """the flat fp32 gradient arena (all parameters, parameter order) of the forward named by `token`"""
+def _op_backward(dlogits: torch.Tensor, x: torch.Tensor, token: torch.Tensor, handle: int, input_grad: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the flat fp32 gradient arena (all parameters, parameter order) of the forward named by `token`, and the gradient of x in
+    x's shape - an empty tensor unless `input_grad` (what the forward was told) and the plan has the stem's data gradient"""
     m = _module_of(handle)
     plan = m._live.pop(int(token.item()), None)          # (a CPU scalar: no device synchronisation)
     if plan is None:
         raise RuntimeError("mds: the activations of this forward have been released (backward already ran, or the "
                            "plan was reused by a later forward); a second backward / retain_graph is not supported")
     flat = _run_backward(m, plan, x, dlogits)
+    dx = _input_grad(plan, x) if input_grad else None
     plan.in_flight = False
-    return flat
+    return flat, (dx if dx is not None else x.new_empty((0,)))
 
 
 @_op_backward.register_fake
-def _(dlogits, x, token, handle):
-    return dlogits.new_empty((sum(p.numel() for p in _module_of(handle).parameters()),), dtype=torch.float32)
+def _(dlogits, x, token, handle, input_grad):
+    m = _module_of(handle)
+    has_dx = input_grad and any(p.requires_grad for p in m.conv2d_encoder.parameters())      # Plan.input_grad's rule
+    return (dlogits.new_empty((sum(p.numel() for p in m.parameters()),), dtype=torch.float32),
+            x.new_empty(x.shape if has_dx else (0,)))
 
 
 def _release_token(handle, token):
@@ -292,7 +305,8 @@ def _release_token(handle, token):
 
 
 def _op_setup_context(ctx, inputs, output):
-    x, params, handle, need_grad, code = inputs
+    x, params, handle, need_grad, code, input_grad = inputs
+    ctx.input_grad = bool(input_grad)
     ctx.save_for_backward(x, output[1])     # x is version-checked: an in-place edit before backward raises
     ctx.handle = handle
     tok = output[1]
@@ -303,15 +317,24 @@ def _op_setup_context(ctx, inputs, output):
 
 def _op_backward_formula(ctx, dlogits, dtoken):
     x, token = ctx.saved_tensors
-    flat = torch.ops.mds.backward(dlogits.contiguous(), x, token, ctx.handle)
+    flat, dx = torch.ops.mds.backward(dlogits.contiguous(), x, token, ctx.handle, ctx.input_grad)
     grads, off = [], 0
     for n, shape, req in ctx.meta:
         grads.append(flat[off:off + n].view(shape) if req else None)
         off += n
-    return None, grads, None, None, None
+    return (dx if ctx.input_grad and dx.numel() else None), grads, None, None, None, None
 
 
 _op_forward.register_autograd(_op_backward_formula, setup_context=_op_setup_context)
+
+
+def _input_grad(plan, x):
+    """the gradient of the frame tensor after the 2D backward chain of `plan` has been issued, in x's (B,T,H,W) shape - a copy: the
+    plan's buffer is rewritten by the next step.  None for a plan without the stem's data gradient.  Under data parallelism it
+    is the rank's own (each rank differentiates its own frames): never all-reduced, it is not part of the gradient arena."""
+    if not plan.input_grad:
+        return None
+    return plan.dx.tensor.view(x.shape).clone()
 
 
 def _run_backward(module, plan, x, dlogits):
@@ -413,6 +436,7 @@ class MultiDimStacker(nn.Module):
         self._handle = next(_HANDLES)
         self._live = {}                       # token -> plan of a grad-enabled forward whose backward has not run yet
         self._warned_fp16 = False
+        self._warned_input_grad = False
         _MODULES[self._handle] = self
 
     def __deepcopy__(self, memo):             # src/ema.py:40 deep-copies the module: the copy is its own operator target
@@ -465,12 +489,14 @@ class MultiDimStacker(nn.Module):
             return cabi.MDS_BF16
         return cabi.MDS_F32
 
-    def _plan(self, x, kind, B, T, H, W, need_grad, ingest=None, code=None):
+    def _plan(self, x, kind, B, T, H, W, need_grad, ingest=None, code=None, input_grad=False):
         lib = self._library(x)
         enc_grad = any(p.requires_grad for p in self.conv2d_encoder.parameters())
         code = self._code() if code is None else code
         opts = PlanOptions.of(self, self.training, need_grad)
-        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, x.device, ingest, opts)
+        # (the frames require grad AND the 2D backward chain exists - Plan.input_grad's rule: a property of the call, not a switch)
+        input_grad = bool(input_grad) and bool(need_grad) and enc_grad and kind in ("full", "2d")
+        key = (kind, B, T, H, W, code, self.training, need_grad, enc_grad, input_grad, x.device, ingest, opts)
         cache = self._cache
         pool = cache.plans.setdefault(key, [])
         cache.plans.move_to_end(key)
@@ -478,7 +504,8 @@ class MultiDimStacker(nn.Module):
             if not plan.in_flight and not plan.stale():
                 return plan
         pool[:] = [p for p in pool if not p.stale()]
-        plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, options=opts)
+        plan = Plan(self, lib, x.device, kind, B, T, H, W, code, self.training, need_grad, enc_grad, ingest=ingest, options=opts,
+                    input_grad=input_grad)
         pool.append(plan)
         cache.evict(key)
         return plan
@@ -509,20 +536,35 @@ class MultiDimStacker(nn.Module):
         self.rng_draws = draw + 1
         return self.rng_seed, int(getattr(self, "rng_stream", 0)) & 0xFFFFFFFF, draw
 
+    def _wants_input_grad(self, x):
+        """x requires grad under grad mode - and the 2D backward chain that ends in the stem's data gradient exists.  With a frozen
+        2D encoder that chain is pruned from the plan: x.grad stays None, said once per instance, not silently."""
+        if not (torch.is_grad_enabled() and x.requires_grad):
+            return False
+        if any(p.requires_grad for p in self.conv2d_encoder.parameters()):
+            return True
+        if not getattr(self, "_warned_input_grad", False) and not torch.compiler.is_compiling():
+            self._warned_input_grad = True
+            warnings.warn("mds.MultiDimStacker: the input requires grad but the 2D encoder is frozen - its backward chain is not "
+                          "built, so no input gradient is computed (x.grad stays None). Leave the encoder's parameters trainable "
+                          "to get the input gradient.", RuntimeWarning, stacklevel=3)
+        return False
+
     # ------------------------------------------------------------------ reference API
     def forward(self, x):
         b, t, h, w = x.shape
         assert t == self.num_frames and t % self.stack_size == 0
         x = x.float().contiguous()
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        input_grad = self._wants_input_grad(x)       # (implies need_grad: the encoder's parameters require grad)
         if USE_CUSTOM_OP:      # the registered operator: traceable by torch.compile(fullgraph=True), one opaque node each way
-            return torch.ops.mds.forward(x, list(self.parameters()), self._handle, need_grad, self._code())[0]
-        return self._forward_untraced(x, need_grad)
+            return torch.ops.mds.forward(x, list(self.parameters()), self._handle, need_grad, self._code(), input_grad)[0]
+        return self._forward_untraced(x, need_grad, input_grad)
 
     @torch.compiler.disable
-    def _forward_untraced(self, x, need_grad):
+    def _forward_untraced(self, x, need_grad, input_grad=False):
         b, t, h, w = x.shape
-        plan = self._plan(x, "full", b, t, h, w, need_grad)
+        plan = self._plan(x, "full", b, t, h, w, need_grad, input_grad=input_grad)
         if need_grad:
             return _MDSFunction.apply(x, self, plan, *plan.params)
         with plan.device_guard():
@@ -539,7 +581,7 @@ class MultiDimStacker(nn.Module):
         names = self.SUB_PARAMS[kind]
         params = [p for n, p in self.named_parameters() if n.startswith(names)]
         need_grad = torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in params))
-        plan = self._plan(inp, kind, B, T, H, W, need_grad)
+        plan = self._plan(inp, kind, B, T, H, W, need_grad, input_grad=kind == "2d" and self._wants_input_grad(inp))
         if need_grad:
             return _SubFunction.apply(inp, self, plan, kind, *params)
         return self._run_sub(plan, kind, inp)

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 137
+#define MDS_VERSION 138
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -385,12 +385,31 @@ typedef struct {
   const void* dy; /* [N][OH][OW][Cout] */
   float* dw;      /* [Cout][3][3][3] fp32 (OIHW) */
   mds_dyp_t dyp;  /* dyp.mode == 1: dy is formed on load from the stem BatchNorm's backward inputs (`dy` ignored):
-                     dy = A*g + B*y + D with g = u (MDS_G_PLAIN) or u*silu'(y*scale + shift) (MDS_G_SILU) - the stem has no
-                     data gradient, so its BatchNorm-backward apply pass would only feed this kernel (bf16 path)          */
+                     dy = A*g + B*y + D with g = u (MDS_G_PLAIN) or u*silu'(y*scale + shift) (MDS_G_SILU) - besides this kernel only
+                     mds_stem_dgrad reads the stem's dy, and it forms it the same way: no BatchNorm-backward apply pass (bf16 path) */
   mds_partial_t partial; /* optional fixed-order way out (deterministic training); buf == NULL: atomics */
 } mds_stem_wgrad_args;
 int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream);
 long mds_stem_wgrad_partial_floats(const mds_stem_wgrad_args* a);
+
+/* data gradient of the stem: dx[n][p][iy][ix] = sum_{ky,kx} sum_o w[o][p][ky][kx] * dy[n][oy][ox][o] with oy = (iy + pad_t - ky) / 2,
+ * ox = (ix + pad_l - kx) / 2, over the taps whose two divisions are exact and 0 <= oy < OH, 0 <= ox < OW (the transposed 3x3
+ * stride-2 TF-SAME convolution; replaces the input half of aten::convolution_backward behind conv_stem).  A gather: no atomics,
+ * every element of dx is written exactly once (dx needs no initialisation), each sum runs in a fixed order (o ascending, then
+ * ky, then kx) - two launches give the same bits.  dx is fp32 whatever `dtype`: the gradient of the caller's (B,T,H,W) frame
+ * stack seen as triples.  dy is given as to mds_stem_wgrad: materialised, or formed on load (dyp.mode == 1, both dtypes; the
+ * formed value is rounded to the storage type, as the materialised tensor would have been).  dy / u / y / bn / lin 16-byte
+ * aligned; pad_t, pad_l in {0, 1}.  Returns 0 or a negative MDS_ERR_* code.                                                */
+typedef struct {
+  int dtype;
+  int N, H, W, OH, OW, Cout; /* Cout = 16 or 32 */
+  int pad_t, pad_l;
+  const void* w;  /* [Cout][32] packed as for mds_stem_fwd (MDS_PACK_STEM) */
+  const void* dy; /* [N][OH][OW][Cout] */
+  float* dx;      /* [N][3][H][W] fp32 */
+  mds_dyp_t dyp;
+} mds_stem_dgrad_args;
+long mds_stem_dgrad(const mds_stem_dgrad_args* a, mds_stream_t stream);
 
 /* ---- expansion prologue of the 2D depthwise forward (inference plans; mds_dw_fwd_args.expand): the block's narrow
  * input x is expanded in the same launch, y1 = silu((x * w^T)[c] * scale[c] + shift[c]), one tile of output pixels and
