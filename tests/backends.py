@@ -1,5 +1,7 @@
 """Backends for the kernel tests: 'emu' = the same kernel sources run through the host simulator
 (CPU tensors, no GPU needed); 'gpu' = the hipcc-built gfx950 library on cuda:0 (pytest -m gpu)."""
+import contextlib
+
 import pytest
 import torch
 
@@ -33,6 +35,35 @@ class Backend:
         if dtype is not None:
             x = x.to(dtype)
         return x.contiguous()
+
+
+    def launches(self, name=None):
+        """simulator only: the launches since the last knobs() entry / reset_launches(), optionally those whose kernel expression
+        contains `name`; None on the GPU (the same host routing code runs there, but nothing records it)"""
+        if self.name != "emu":
+            return None
+        from hipemu.loader import launches
+        return [l for l in launches() if name is None or name in l.kernel]
+
+    def reset_launches(self):
+        if self.name == "emu":
+            from hipemu.loader import reset_launches
+            reset_launches()
+
+
+@contextlib.contextmanager
+def knobs(be, values):
+    """developer knobs ({MDS_KNOB_*: value}) for the body of a `with`; every one is back at 0 afterwards, also when the body
+    raises - the knobs are process-global per library, and a failing test must not leak them into the next.  Clears the
+    simulator's launch record on entry, so that be.launches() inside the body sees the body's launches only."""
+    be.reset_launches()
+    try:
+        for k, v in values.items():
+            be.lib.check(be.lib.fn["dev_set"](k, v), "dev_set")
+        yield
+    finally:
+        for k in values:
+            be.lib.fn["dev_set"](k, 0)
 
 
 BACKENDS = ["emu", pytest.param("gpu", marks=pytest.mark.gpu)]

@@ -198,8 +198,17 @@ inline void run_block(BlockState& b) {
   g_blk = nullptr;
 }
 
-inline void launch(dim3 grid, dim3 block, size_t smem, std::function<void()> body) {
+// Launch record: what MDS_LAUNCH was asked to run since the last reset (kernel expression as written at the call site, grid,
+// block.x), so that a test which forces a launch geometry through a developer knob can assert that it got it.  Read from Python
+// through the three hipemu_launch_* exports below (libmds_emu.so only - not part of include/mds.h).  Bounded: launches past
+// kLaunchCap are run but not remembered.
+struct LaunchRec { const char* kernel; unsigned gx, gy, gz, bx; };
+inline std::vector<LaunchRec> g_launches;
+static const size_t kLaunchCap = 1 << 16;
+
+inline void launch(const char* kernel, dim3 grid, dim3 block, size_t smem, std::function<void()> body) {
   static BlockState b;
+  if (g_launches.size() < kLaunchCap) g_launches.push_back({kernel, grid.x, grid.y, grid.z, block.x});
   int n = block.x * block.y * block.z;
   if ((int)b.fibers.size() < n) {
     size_t old = b.fibers.size();
@@ -243,6 +252,19 @@ inline T shfl_src(T v, int src_lane) {
 }
 
 }  // namespace hipemu
+
+// every translation unit of the simulator build emits these (inline + used); the linker keeps one copy and one record
+extern "C" {
+__attribute__((used, visibility("default"))) inline int hipemu_launch_count() { return (int)hipemu::g_launches.size(); }
+__attribute__((used, visibility("default"))) inline void hipemu_launch_reset() { hipemu::g_launches.clear(); }
+// entry i: returns the kernel string (NULL when i is out of range), dims[0..3] = grid.x, grid.y, grid.z, block.x
+__attribute__((used, visibility("default"))) inline const char* hipemu_launch_get(int i, unsigned* dims) {
+  if (i < 0 || (size_t)i >= hipemu::g_launches.size()) return nullptr;
+  const hipemu::LaunchRec& r = hipemu::g_launches[i];
+  dims[0] = r.gx; dims[1] = r.gy; dims[2] = r.gz; dims[3] = r.bx;
+  return r.kernel;
+}
+}
 
 inline void __syncthreads() { hipemu::block_barrier(); }
 template <typename T> inline T __shfl_xor(T v, int mask, int width = 64) { (void)width; return hipemu::shfl_src(v, hipemu::lane_id() ^ mask); }

@@ -1,5 +1,7 @@
 """TEST INFRASTRUCTURE: builds and opens libmds_emu.so, the host simulator build of csrc/*.hip
 (see hipemu.h).  Only the test-suite uses this; the product loader (mds.cabi.load) cannot."""
+import collections
+import ctypes
 import os
 import subprocess
 
@@ -16,3 +18,21 @@ def load_emulator():
         from mds.cabi import Lib
         _LIB = Lib(os.path.join(HERE, "libmds_emu.so"))
     return _LIB
+
+
+Launch = collections.namedtuple("Launch", "kernel gx gy gz bx")
+
+
+def launches():
+    """the simulator's launch record since the last reset_launches(): [Launch(kernel expression, grid.x, grid.y, grid.z, block.x)]"""
+    dll = load_emulator().dll
+    dll.hipemu_launch_get.restype = ctypes.c_char_p
+    dll.hipemu_launch_get.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint)]
+    out, dims = [], (ctypes.c_uint * 4)()
+    for i in range(dll.hipemu_launch_count()):
+        out.append(Launch(dll.hipemu_launch_get(i, dims).decode(), *dims))
+    return out
+
+
+def reset_launches():
+    load_emulator().dll.hipemu_launch_reset()

@@ -73,31 +73,32 @@ def test_dw_fwd_six_row_bands(be, dt, N, T, H, W, C, stride, kt):
         be.lib.fn["dev_set"](cabi.MDS_KNOB_DW2_R, 0)
 
 
-def _dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt):
+def _dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt, rd=torch.float32):
+    """rd: the type the reference is computed in (float64 in tests/test_launch_geometry.py)"""
     code, tdt = DT[dt]
     g = gen(H * W + C + kt)
     x = (torch.randn(N, C, T, H, W, generator=g) * 1.3).to(tdt)
     w = torch.randn(C, 1, kt, 3, 3, generator=g) * 0.3
-    gamma = 1 + 0.2 * torch.randn(C, generator=g); beta = 0.2 * torch.randn(C, generator=g)
+    gamma = (1 + 0.2 * torch.randn(C, generator=g)).to(rd); beta = (0.2 * torch.randn(C, generator=g)).to(rd)
     eps = 1e-3
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
     pads = (geo.same_pad(H, stride), geo.same_pad(W, stride)) if stride == 2 else ((1, 1), (1, 1))
     # reference: a = silu(bn(x)) with the batch statistics held constant; y = dw(a)
-    xf = x.float()
-    wf = w.clone().requires_grad_(True)
+    xf = x.to(rd)
+    wf = w.to(rd).requires_grad_(True)
     mean = xf.mean((0, 2, 3, 4)); var = xf.var((0, 2, 3, 4), unbiased=False)
     rstd = 1 / torch.sqrt(var + eps)
     scale = gamma * rstd; shift = beta - mean * scale
     z = (xf * scale.view(1, -1, 1, 1, 1) + shift.view(1, -1, 1, 1, 1)).requires_grad_(True)
     a = F.silu(z)
     if dt == "bf16":
-        a = a + (a.detach().to(tdt).float() - a.detach())               # bf16-rounded activations
+        a = a + (a.detach().to(tdt).to(rd) - a.detach())               # bf16-rounded activations
     yref = dw_ref(a, wf, stride, kt, pads)
     dyt = torch.randn(yref.shape, generator=g).to(tdt)
-    yref.backward(dyt.float())
+    yref.backward(dyt.to(rd))
     # forward kernel
     xd = be.t(to_rows(x)); wd = be.t(w.view(C, kt * 9))
-    scd, shd = be.t(scale), be.t(shift)
+    scd, shd = be.t(scale.float()), be.t(shift.float())
     y = torch.full((N, T, OH, OW, C), float("nan")).to(tdt).to(be.device)
     st = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)
     pro = cabi.pro(2, scd, shd)
@@ -116,7 +117,7 @@ def _dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt):
     st2 = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)     # backward sums: fp64 slots
     be.call("dw_bwd", cabi.make("mds_dw_bwd_args", dtype=code, N=N, T=T, IH=H, IW=W, C=C, OH=OH, OW=OW, stride=stride,
                                 pad_t=pt, pad_l=pl, kt=kt, x=xd, dy=be.t(to_rows(dyt)), w=wd, g=gout, dw=dw, pro=pro,
-                                mean=be.t(mean), rstd=be.t(rstd), stats=st2))
+                                mean=be.t(mean.float()), rstd=be.t(rstd.float()), stats=st2))
     be.sync()
     gref = to_rows(z.grad)
     assert_close(gout, gref, dt, msg="g")
@@ -155,18 +156,19 @@ def test_dw_fwd_output_transform(be, dt, N, T, H, W, C, stride, kt):
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("N,H,W", [(2, 20, 36), (1, 17, 23), (3, 6, 70), (2, 40, 150)])      # (the last: 3 x 3 tiles of the tiled kernels per image)
-def test_stem_fwd_wgrad(be, dt, N, H, W):
+def test_stem_fwd_wgrad(be, dt, N, H, W, rd=torch.float32):
+    """rd: the type the reference is computed in (float64 in tests/test_launch_geometry.py)"""
     code, tdt = DT[dt]
     g = gen(H * W)
     x = torch.rand(N, 3, H, W, generator=g)
     w = torch.randn(32, 3, 3, 3, generator=g) * 0.3
     OH, OW, pt, pl = geo.conv_geometry(H, W, 2)
     (pt_, pb), (pl_, pr) = geo.same_pad(H, 2), geo.same_pad(W, 2)
-    xq = x.to(tdt).float()
-    wq = w.to(tdt).float().requires_grad_(True)
+    xq = x.to(tdt).to(rd)
+    wq = w.to(tdt).to(rd).requires_grad_(True)
     yref = F.conv2d(F.pad(xq, (pl_, pr, pt_, pb)), wq, None, 2)
     dyt = torch.randn(yref.shape, generator=g).to(tdt)
-    yref.backward(dyt.float())
+    yref.backward(dyt.to(rd))
     wp = torch.zeros(32, 32); wp[:, :27] = w.view(32, 27)
     y = torch.full((N, OH, OW, 32), float("nan")).to(tdt).to(be.device)
     st = torch.zeros(SLOTS, 2, 32, device=be.device, dtype=torch.float64)

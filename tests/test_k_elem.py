@@ -214,6 +214,126 @@ def test_bn_backward_chain(be, dt, mode, C):
     assert_close(dy, yf.grad, dt, scale=2, msg="dy")
 
 
+def bn_bwd_reference(y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, running=None):
+    """float64 autograd through act(batch_norm(y)) for the four gradient sources of mds_gsrc_t -> dy, dgamma, dbeta, on exactly
+    the stored y and u; running = (mean, var): eval-mode BatchNorm (the statistics are constants)"""
+    F64 = torch.float64
+    M = y.shape[0]
+    yd = y.to(F64).requires_grad_(True)
+    gam = gamma.to(F64).requires_grad_(True); bet = beta.to(F64).requires_grad_(True)
+    if running is None:
+        z = F.batch_norm(yd, None, None, gam, bet, True, 0.1, eps)
+    else:
+        z = F.batch_norm(yd, running[0].to(F64), running[1].to(F64), gam, bet, False, 0.1, eps)
+    grp = torch.arange(M) // rpg
+    ud = u.to(F64)
+    if mode == cabi.MDS_G_PLAIN:
+        z.backward(ud)
+    elif mode == cabi.MDS_G_SILU:
+        F.silu(z).backward(ud)
+    elif mode == cabi.MDS_G_SE_SILU:
+        F.silu(z).backward(ud * gate.to(F64)[grp] + dpool.to(F64)[grp])
+    else:
+        (z * mask.to(F64)[grp, None]).backward(ud)
+    return yd.grad, gam.grad, bet.grad
+
+
+def _bn_bwd_chain(be, dt, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, use64=False, running=None):
+    """reduce -> finalize -> apply; use64: with fwd_stats / coef64 (the fp64 means of the fp32 training plans, engine.py);
+    running = (mean, var): batch_stats = 0 on the table of mds_bn_finalize(training = 0).  -> dy, dgamma, dbeta, coef, lin"""
+    code, tdt = DT[dt]
+    M, C = y.shape
+    fwd = torch.zeros(SLOTS, 2, C, dtype=torch.float64)
+    fwd[0, 0] = y.double().sum(0); fwd[0, 1] = (y.double() ** 2).sum(0)
+    fwd = be.t(fwd)
+    if running is None:
+        bn = bn_finalize(be, fwd, M, be.t(gamma), be.t(beta), eps=eps)
+    else:
+        bn = bn_finalize(be, None, 0, be.t(gamma), be.t(beta), eps=eps, training=0, rm=be.t(running[0]), rv=be.t(running[1]))
+    gs = cabi.gsrc(mode, be.t(u), be.t(gate) if gate is not None else None, be.t(dpool) if dpool is not None else None,
+                   be.t(mask) if mask is not None else None, rpg)
+    st2 = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)
+    yd = be.t(y)
+    be.call("bn_bwd_reduce", cabi.make("mds_bn_bwd_reduce_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, stats=st2))
+    dgamma = torch.zeros(C, device=be.device); dbeta = torch.zeros(C, device=be.device)
+    coef = torch.full((3, C), float("nan"), device=be.device); lin = torch.full((3, C), float("nan"), device=be.device)
+    coef64 = torch.full((3, C), float("nan"), device=be.device, dtype=torch.float64) if use64 else None
+    be.call("bn_bwd_finalize", cabi.make("mds_bn_bwd_finalize_args", C=C, count=M, stats=st2, gamma=be.t(gamma), bn=bn, dgamma=dgamma,
+                                         dbeta=dbeta, coef=coef, lin=lin, batch_stats=0 if running is not None else 1,
+                                         fwd_stats=fwd if use64 else None, coef64=coef64))
+    dy = torch.full((M, C), float("nan")).to(tdt).to(be.device)
+    be.call("bn_bwd_apply", cabi.make("mds_bn_bwd_apply_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, coef=coef, dy=dy, coef64=coef64))
+    be.sync()
+    return dy, dgamma, dbeta, coef, lin
+
+
+def _bn_bwd_inputs(M, C, rpg, tdt, seed):
+    g = gen(seed)
+    G = (M + rpg - 1) // rpg
+    y = (torch.randn(M, C, generator=g) * 1.5 + 0.3).to(tdt)
+    u = torch.randn(M, C, generator=g).to(tdt)
+    gamma = 1 + 0.2 * torch.randn(C, generator=g); beta = 0.2 * torch.randn(C, generator=g)
+    gate = torch.rand(G, C, generator=g); dpool = 0.1 * torch.randn(G, C, generator=g)
+    mask = (torch.rand(G, generator=g) > 0.3).float() / 0.7
+    return g, y, u, gamma, beta, gate, dpool, mask
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+def test_bn_backward_chain_fp64_means(be, mode):
+    """mds_bn_bwd_finalize_args.fwd_stats / coef64 and mds_bn_bwd_apply_args.coef64 (every fp32 training plan passes them): the
+    batch mean from the forward pass's fp64 sums, sum g / M and sum g * xhat / M in fp64, subtracted in fp64 in the apply pass -
+    against float64 autograd for every g-source, at the fp32 tolerance of test_bn_backward_chain"""
+    M, C, rpg, eps = 330, 40, 110, 1e-5
+    _, y, u, gamma, beta, gate, dpool, mask = _bn_bwd_inputs(M, C, rpg, torch.float32, 61 + mode)
+    dy_ref, dgamma_ref, dbeta_ref = bn_bwd_reference(y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps)
+    dy, dgamma, dbeta, _, _ = _bn_bwd_chain(be, "f32", y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, use64=True)
+    assert_close(dgamma, dgamma_ref, "f32", scale=20, msg="dgamma")
+    assert_close(dbeta, dbeta_ref, "f32", scale=20, msg="dbeta")
+    assert_close(dy, dy_ref, "f32", scale=2, msg="dy")
+
+
+def test_bn_backward_fp64_means_keep_the_column_sums(be):
+    """what coef64 is there for: the fp32-rounded means are the SAME for every row, so their rounding error adds up M times in
+    every column sum of dy (the bias gradients upstream).  A per-channel offset in y (mean ~ 10: half an ulp is 5e-7) and a
+    gradient that correlates with y and has a mean of its own (sum g / M and sum g * xhat / M of order 1) make that error
+    M * ~1e-7 per channel against ~sqrt(M) * 2e-8 from the one rounding per element that both forms share - at M = 20 000 rows
+    two orders of magnitude apart.  In exact arithmetic every column sum of dy is zero."""
+    M, C, rpg, eps = 20000, 16, 20000, 1e-5
+    g = gen(71)
+    off = 8 + 4 * torch.rand(C, generator=g)
+    y = torch.randn(M, C, generator=g) + off
+    u = torch.randn(M, C, generator=g) + 0.5 * (y - off) + 1.0
+    gamma = 1 + 0.2 * torch.randn(C, generator=g); beta = 0.2 * torch.randn(C, generator=g)
+    dy_ref, dgamma_ref, dbeta_ref = bn_bwd_reference(y, u, gamma, beta, 0, None, None, None, rpg, eps)
+    err = {}
+    for use64 in (False, True):
+        dy, dgamma, dbeta, _, _ = _bn_bwd_chain(be, "f32", y, u, gamma, beta, 0, None, None, None, rpg, eps, use64=use64)
+        assert_close(dy, dy_ref, "f32", scale=2, msg=f"dy (coef64: {use64})")
+        assert_close(dgamma, dgamma_ref, "f32", scale=20, msg="dgamma"); assert_close(dbeta, dbeta_ref, "f32", scale=20, msg="dbeta")
+        err[use64] = float((dy.cpu().double().sum(0) - dy_ref.sum(0)).abs().max())
+    assert err[True] <= err[False], f"worst column sum of dy: {err[True]:.3e} off the float64 sum with coef64, {err[False]:.3e} without"
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", [1, 3])
+def test_bn_backward_eval_mode(be, dt, mode):
+    """mds_bn_bwd_finalize_args.batch_stats = 0: the BatchNorm backward of the frozen-encoder configuration - running statistics
+    (the table of mds_bn_finalize with training = 0) are constants, so coef1 = coef2 = 0 and dy = gamma * rstd * g; dgamma / dbeta
+    are still the sums; lin = {A, 0, 0}"""
+    code, tdt = DT[dt]
+    M, C, rpg, eps = 330, 40, 110, 1e-5
+    g, y, u, gamma, beta, gate, dpool, mask = _bn_bwd_inputs(M, C, rpg, tdt, 81 + mode)
+    rm = 0.3 + 0.2 * torch.randn(C, generator=g); rv = 1.5 + torch.rand(C, generator=g)
+    dy_ref, dgamma_ref, dbeta_ref = bn_bwd_reference(y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, running=(rm, rv))
+    dy, dgamma, dbeta, coef, lin = _bn_bwd_chain(be, dt, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, running=(rm, rv))
+    assert_close(dgamma, dgamma_ref, dt, scale=20, msg="dgamma")
+    assert_close(dbeta, dbeta_ref, dt, scale=20, msg="dbeta")
+    assert_close(dy, dy_ref, dt, scale=2, msg="dy")
+    A = gamma.double() / torch.sqrt(rv.double() + eps)
+    assert_close(coef[0], A, "f32", msg="coef0"); assert_close(lin[0], A, "f32", msg="A")
+    assert float(coef[1:].abs().sum()) == 0.0 and float(lin[1:].abs().sum()) == 0.0, "coef1 = coef2 = 0, B = D = 0"
+
+
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("pro_mode,split,R_,C", [(0, False, 35, 16), (2, False, 35, 16), (2, True, 35, 16), (2, True, 920, 64)])
 def test_gem_fwd_bwd(be, dt, pro_mode, split, R_, C, golden):
