@@ -26,6 +26,15 @@
  *    (`pooled`), its backward (`dgate`) and the row-split GeM accumulators: all fp64.  What is left to fp32 atomics
  *    are the parameter-gradient accumulations (weight-gradient arena, GeM's dp), which feed nothing else in the step -
  *    and those have a second, fixed-order way out (mds_partial_t below) for runs that must repeat bit for bit.
+ *  - Alignment.  16 bytes: activations, residuals, filters and packed weights, the per-channel fp32 tables (scale / shift /
+ *    bn / coef / lin / gate / dpooled) and the fp64 buffers (stats, pooled, dgate, accum) - the kernels move them in 16-byte
+ *    vectors.  4 bytes: the fp32 buffers a planner carves densely out of arenas, which the kernels reach by scalar loads,
+ *    stores and atomics only - every parameter gradient (dw of mds_pw_wgrad / mds_conv_wgrad / mds_stem_wgrad / mds_dw_bwd,
+ *    dgamma / dbeta of mds_bn_bwd_finalize, dw1 / db1 / dw2 / db2 of mds_se_fc_bwd_params and its table, dp of mds_gem_bwd,
+ *    dw / db of mds_head_bwd) and every per-group mask that is READ (mds_bn_res_args.mask, mds_gsrc_t.mask,
+ *    mds_poststat_t.mask, mask of mds_head_fwd / mds_head_bwd).  A field that asks for more says so where it is declared
+ *    (mds_partial_t.buf, mds_mask_fill's arena, mds_wgrad_finish's partial, the squeeze-excite tail);
+ *    tests/test_arena_placement.py holds every 4-byte field at an address = 4 mod 16.
  */
 #ifndef MDS_H
 #define MDS_H

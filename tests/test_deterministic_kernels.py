@@ -33,7 +33,10 @@ class DetBackend:
 
     stream = lambda self: self.be.stream()
     sync = lambda self: self.be.sync()
-    t = lambda self, x, dtype=None: self.be.t(x, dtype)
+    t = lambda self, x, dtype=None, **kw: self.be.t(x, dtype, **kw)
+    out = lambda self, *a, **kw: self.be.out(*a, **kw)
+    ptr = lambda self, t: self.be.ptr(t)
+    rc = lambda self, op, args: self.be.rc(op, args)
 
     def call(self, op, args):
         if op not in RESULT:
@@ -51,12 +54,16 @@ class DetBackend:
             for p, t in tensors.items():
                 t.detach().copy_(saved[p])
 
+        keep = list(args._keep)
+
         def det():
-            part = torch.full((need,), float("nan"), dtype=torch.float32, device=self.device)
+            part = self.be.out(need, torch.float32, float("nan"))
             args.partial = cabi.make("mds_partial_t", buf=part, floats=need)
+            args._keep = keep + [part]                   # (assigned after cabi.make: be.call must see the slots too)
             self.be.call(op, args)
             self.be.sync()
             args.partial = cabi.make("mds_partial_t", buf=None, floats=0)
+            args._keep = keep
             return res.clone()
 
         self.be.call(op, args)                      # 1. atomics
@@ -84,14 +91,25 @@ def det(request):
     name = request.param
     if name not in _cache:
         _cache[name] = Backend(name)
-    return DetBackend(_cache[name])
+    yield DetBackend(_cache[name])
+    _cache[name].finish()
 
 
 @pytest.fixture
 def det_gpu():
     if "gpu" not in _cache:
         _cache["gpu"] = Backend("gpu")
-    return DetBackend(_cache["gpu"])
+    yield DetBackend(_cache["gpu"])
+    _cache["gpu"].finish()
+
+
+@pytest.fixture
+def emu():
+    """the simulator's backend for the tests below that never run on the GPU: guarded buffers, verified on teardown"""
+    if "emu" not in _cache:
+        _cache["emu"] = Backend("emu")
+    yield _cache["emu"]
+    _cache["emu"].finish()
 
 
 def cases(fn, *more):
@@ -121,43 +139,43 @@ def test_abi_declares_and_exports_the_deterministic_way_out():
     assert not hip.missing and "wgrad_finish" in hip.fn
 
 
-def test_undersized_or_misaligned_partial_buffer_is_a_bad_argument():
-    from hipemu.loader import load_emulator
-    lib = load_emulator()
+def test_undersized_or_misaligned_partial_buffer_is_a_bad_argument(emu):
+    lib = emu.lib
     M, K, N = 700, 40, 72
-    x, dy, dw = torch.randn(M, K), torch.randn(M, N), torch.zeros(N, K)
+    x, dy, dw = emu.t(torch.randn(M, K)), emu.t(torch.randn(M, N)), emu.out((N, K), torch.float32, 0)
     args = cabi.make("mds_pw_wgrad_args", dtype=0, M=M, K=K, N=N, x=x, dy=dy, dw=dw, pro=cabi.pro(0))
     need = lib.fn["pw_wgrad_partial_floats"](C.byref(args))
     assert need >= N * K
-    part = torch.zeros(need + 4)
+    part = emu.out(need + 4, torch.float32, 0)
+    args._keep = args._keep + [part]
     args.partial = cabi.make("mds_partial_t", buf=part, floats=need - 1)
-    assert lib.fn["pw_wgrad"](C.byref(args), 0) == cabi.MDS_ERR_BAD_ARG and b"partial" in lib.dll.mds_last_error()
+    assert emu.rc("pw_wgrad", args) == cabi.MDS_ERR_BAD_ARG and b"partial" in lib.dll.mds_last_error()
     assert torch.equal(dw, torch.zeros(N, K)), "a refused launch wrote the gradient"
     args.partial = cabi.make("mds_partial_t", buf=part[1:], floats=need)
-    assert lib.fn["pw_wgrad"](C.byref(args), 0) == cabi.MDS_ERR_BAD_ARG
+    assert emu.rc("pw_wgrad", args) == cabi.MDS_ERR_BAD_ARG
     args.partial = cabi.make("mds_partial_t", buf=part, floats=need)
-    assert lib.fn["pw_wgrad"](C.byref(args), 0) == 0
+    assert emu.rc("pw_wgrad", args) == 0
+    emu.sync()
     assert_close(dw, dy.t() @ x, "f32", scale=M ** 0.5)
     # the query reads dims only: a struct without buffers gives the same answer
     bare = cabi.make("mds_pw_wgrad_args", dtype=0, M=M, K=K, N=N, pro=cabi.pro(0))
     assert lib.fn["pw_wgrad_partial_floats"](C.byref(bare)) == need
 
 
-def test_wgrad_finish_adds_the_slots_in_slot_order():
+def test_wgrad_finish_adds_the_slots_in_slot_order(emu):
     """mds_wgrad_finish on its own, against the order its header comment states: G contiguous slot ranges (G from the result's
     size), each summed first to last, the range sums added first to last, the total added to the destination - bit for bit,
     aligned and unaligned, in all three size classes, with fewer slots than ranges and with ranges of unequal length"""
-    from hipemu.loader import load_emulator
-    lib = load_emulator()
     g = torch.Generator().manual_seed(5)
     for numel, slots, off in ((1, 7, 0), (1, 200, 0), (1030, 9, 0), (1030, 2, 1), (516, 13, 0), (27 * 32, 1, 3), (864, 768, 0), (672 * 9, 131, 0),
                                (4096, 37, 0), (5000, 70, 1), (65536, 5, 0), (65540, 9, 3)):
         stride = (numel + 3) // 4 * 4
         part = (torch.randn(slots, stride, generator=g) * 10 ** torch.randint(-3, 4, (slots, 1), generator=g).float()).contiguous()
         base = torch.randn(numel + off, generator=g)
-        dst = base.clone()
-        a = cabi.make("mds_wgrad_finish_args", partial=part, dst=dst[off:], numel=numel, slots=slots, slot_stride=stride)
-        assert lib.fn["wgrad_finish"](C.byref(a), 0) == 0, lib.dll.mds_last_error()
+        dst = emu.out(numel + off, torch.float32, base)
+        a = cabi.make("mds_wgrad_finish_args", partial=emu.t(part), dst=dst[off:], numel=numel, slots=slots, slot_stride=stride)
+        assert emu.rc("wgrad_finish", a) == 0, emu.lib.dll.mds_last_error()
+        emu.sync()
         G = cabi.MDS_FINISH_GROUPS if numel >= cabi.MDS_FINISH_WIDE else cabi.MDS_FINISH_GROUPS_MID if numel >= cabi.MDS_FINISH_MID else cabi.MDS_FINISH_GROUPS_SMALL
         per = -(-slots // G)
         total = None
@@ -213,24 +231,25 @@ def test_c3w2_stride2(det, N, H, W, blocks):
     assert len(det.launches) == 1
 
 
-def test_ablation_switches_are_refused_not_composed():
+def test_ablation_switches_are_refused_not_composed(emu):
     """MDS_KNOB_WG_DBG's ablation bits skip the kernel's sums or stores: with a partial buffer that would leave slots unwritten, so
     the launch is a clear error (the atomic path keeps its meaning: measurement only)"""
-    from hipemu.loader import load_emulator
-    lib = load_emulator()
+    lib = emu.lib
     M, K, N = 600, 32, 64
-    x, dy, dw = torch.randn(M, K).bfloat16(), torch.randn(M, N).bfloat16(), torch.zeros(N, K)
+    x, dy, dw = emu.t(torch.randn(M, K).bfloat16()), emu.t(torch.randn(M, N).bfloat16()), emu.out((N, K), torch.float32, 0)
     args = cabi.make("mds_pw_wgrad_args", dtype=1, M=M, K=K, N=N, x=x, dy=dy, dw=dw, pro=cabi.pro(0))
     need = lib.fn["pw_wgrad_partial_floats"](C.byref(args))
-    part = torch.full((need,), float("nan"))
+    part = emu.out(need, torch.float32, float("nan"))
     args.partial = cabi.make("mds_partial_t", buf=part, floats=need)
+    args._keep = args._keep + [part]
     try:
         for bits in (1, 2, 4):
             lib.check(lib.fn["dev_set"](cabi.MDS_KNOB_WG_DBG, bits), "dev_set")
-            assert lib.fn["pw_wgrad"](C.byref(args), 0) == cabi.MDS_ERR_BAD_ARG and b"WG_DBG" in lib.dll.mds_last_error()
+            assert emu.rc("pw_wgrad", args) == cabi.MDS_ERR_BAD_ARG and b"WG_DBG" in lib.dll.mds_last_error()
             assert torch.equal(dw, torch.zeros(N, K))
         lib.check(lib.fn["dev_set"](cabi.MDS_KNOB_WG_DBG, 32), "dev_set")      # (not an ablation: row splits not rounded to 8 - composes)
-        assert lib.fn["pw_wgrad"](C.byref(args), 0) == 0
+        assert emu.rc("pw_wgrad", args) == 0
+        emu.sync()
     finally:
         lib.fn["dev_set"](cabi.MDS_KNOB_WG_DBG, 0)
     assert_close(dw, dy.float().t() @ x.float(), "bf16", scale=M ** 0.5)
@@ -295,7 +314,7 @@ def test_focal_loss_over_several_blocks(det):
     """2000 elements = 8 blocks add to the loss value: through slots, in block order; against float64"""
     g = torch.Generator().manual_seed(2)
     x, t = torch.randn(2000, generator=g) * 3, (torch.rand(2000, generator=g) > 0.7).float()
-    loss, dx = torch.zeros(1, device=det.device), torch.empty(2000, device=det.device)
+    loss, dx = det.out(1, torch.float32, 0), det.out(2000, torch.float32, float("nan"))
     args = cabi.make("mds_focal_args", n=2000, x=det.t(x), t=det.t(t), alpha=-1.0, gamma=1.2, reduction=cabi.MDS_REDUCE_MEAN, loss=loss, dx=dx)
     det.call("focal_fwd_bwd", args)
     assert det.launches == [("focal_fwd_bwd", 32)]

@@ -20,9 +20,9 @@ DIST_SEED = 42
 
 def _fill(be, keep, seed, stream, draw, n=None, mask=None, **kw):
     n = keep.numel() if n is None else n
-    mask = be.t(torch.full((n,), float("nan"))) if mask is None else mask      # NaN prefill: an unwritten element shows
+    mask = be.out(n, torch.float32, float("nan")) if mask is None else mask      # NaN prefill: an unwritten element shows
     args = cabi.make("mds_mask_fill_args", mask=mask, keep=keep, n=n, seed=seed, stream=stream, draw=draw, **kw)
-    rc = be.lib.fn["mask_fill"](C.byref(args), be.stream())
+    rc = be.rc("mask_fill", args)
     be.sync()
     return rc, mask
 
@@ -66,7 +66,7 @@ def test_kernel_matches_the_host_definition_bit_for_bit(be, n, seed, stream, dra
 def test_fill_writes_n_elements_and_nothing_behind_them(be):
     n = 1001
     keep = torch.full((n + 27,), 0.5)
-    buf = be.t(torch.full((n + 27,), float("nan")))
+    buf = be.out(n + 27, torch.float32, float("nan"))
     rc, _ = _fill(be, be.t(keep), 9, 0, 4, n=n, mask=buf)
     assert rc == 0
     assert torch.equal(buf.cpu()[:n], host.mask(keep[:n], 9, 0, 4)) and torch.isnan(buf.cpu()[n:]).all()
@@ -104,7 +104,7 @@ def test_distribution_of_the_masks(be, p):
 def test_refusals_are_codes_with_a_message(be):
     n = 64
     keep = be.t(torch.full((n + 4,), 0.5))
-    mask = be.t(torch.full((n + 4,), float("nan")))
+    mask = be.out(n + 4, torch.float32, float("nan"))
     err = lambda: be.lib.dll.mds_last_error()
     untouched = lambda: bool(torch.isnan(mask.cpu()).all())
     mk = lambda **kw: cabi.make("mds_mask_fill_args", **dict(dict(mask=mask, keep=keep, n=n, seed=1, stream=0, draw=0), **kw))
@@ -112,12 +112,12 @@ def test_refusals_are_codes_with_a_message(be):
     for kw, word in ((dict(mask=None), b"null"), (dict(keep=None), b"null"), (dict(mask=mask[1:]), b"aligned"), (dict(keep=keep[1:]), b"aligned"),
                      (dict(n=0), b"n =")):
         a = mk(**kw)
-        assert fn(C.byref(a), be.stream()) == cabi.MDS_ERR_BAD_ARG and word in err(), (kw.keys(), err())
+        assert be.rc("mask_fill", a) == cabi.MDS_ERR_BAD_ARG and word in err(), (kw.keys(), err())
     assert fn(None, be.stream()) == cabi.MDS_ERR_BAD_ARG and b"null" in err()
     for bad in (0.0, -0.25, 1.5, float("nan")):
         kp = torch.full((n + 4,), 0.5)
         kp[17] = bad
         a = mk(keep=be.t(kp))
-        assert fn(C.byref(a), be.stream()) == cabi.MDS_ERR_BAD_ARG and b"keep[17]" in err(), (bad, err())
+        assert be.rc("mask_fill", a) == cabi.MDS_ERR_BAD_ARG and b"keep[17]" in err(), (bad, err())
     be.sync()
     assert untouched(), "a refused launch wrote the arena"

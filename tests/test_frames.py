@@ -77,7 +77,7 @@ def test_fetch_into_writes_in_place_any_order_with_repeats(be):
     """the clip is written in its final place (no per-frame tensors, no stack): rows follow the ORDER of `indexes`, a repeated
     index is decoded once, a corrupt frame is a zero row, and the destination may be a view of a larger ring"""
     f, dec = _fetcher(be)
-    ring = torch.full((6, 20, 50), 7, dtype=torch.uint8, device=be.device)
+    ring = be.out((6, 20, 50), torch.uint8, 7)
     idx = [8, 6, 7, 6]
     out = f.fetch_into(idx, ring[1:5])
     be.sync()
@@ -93,7 +93,7 @@ def test_frame_luma_kernel(be, w, h, pitch, count):
     g = torch.Generator().manual_seed(w + h)
     surf = torch.randint(0, 256, (count, h * 3 // 2 + 1, pitch), generator=g, dtype=torch.uint8)
     sd = be.t(surf)
-    dst = torch.full((count, h, w), 7, dtype=torch.uint8, device=be.device)
+    dst = be.out((count, h, w), torch.uint8, 7)
     be.call("frame_luma", cabi.make("mds_frame_luma_args", width=w, height=h, pitch=pitch, count=count, src=sd,
                                     surface_stride=surf.stride(0), dst=dst))
     be.sync()
@@ -111,7 +111,7 @@ def test_copy_rows_kernel(be, row_bytes, src_pitch, dst_pitch, nrows):
     dst0 = torch.randint(0, 256, (ndst, dst_pitch), generator=g, dtype=torch.uint8)
     src_slot = torch.randint(0, nsrc, (nrows,), generator=g).tolist()
     dst_slot = torch.randperm(ndst, generator=g)[:nrows].tolist()
-    sd, dd = be.t(src), be.t(dst0.clone())
+    sd, dd = be.t(src), be.out(dst0.shape, torch.uint8, dst0)
     be.call("copy_rows", cabi.make("mds_copy_rows_args", dst=dd, src=sd, dst_pitch=dst_pitch, src_pitch=src_pitch, row_bytes=row_bytes,
                                    nrows=nrows, dst_slot=dst_slot, src_slot=src_slot))
     be.sync()
@@ -124,7 +124,7 @@ def test_copy_rows_kernel(be, row_bytes, src_pitch, dst_pitch, nrows):
 def test_copy_rows_refuses_more_rows_than_its_argument_block_holds(be):
     t = be.t(torch.zeros(4, 16, dtype=torch.uint8))
     a = cabi.make("mds_copy_rows_args", dst=t, src=t, dst_pitch=16, src_pitch=16, row_bytes=16, nrows=cabi.MDS_COPY_ROWS_MAX + 1)
-    assert be.lib.fn["copy_rows"](a, 0) != 0
+    assert be.rc("copy_rows", a) != 0
 
 
 def test_rocdecode_backend_is_reported_missing_not_faked():

@@ -57,8 +57,8 @@ def test_conv_fwd(be, dt, N, H, W, Cin, Cout, stride, mode):
     scale = 1 + 0.2 * torch.randn(Cin, generator=g); shift = 0.3 * torch.randn(Cin, generator=g)
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
     dy, dx, wi = geo.taps_fwd(pt, pl)
-    y = torch.full((N, OH, OW, Cout), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, Cout, device=be.device, dtype=torch.float64)
+    y = be.out((N, OH, OW, Cout), tdt, float("nan"))
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, Cout), torch.float64, 0)
     args = cabi.make("mds_conv_fwd_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=OH, OW=OW, Cout=Cout,
                      A=OH, B=OW, oy0=0, ox0=0, os=1, **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9,
                      x=be.t(nhwc(x)), w=be.t(pack(w, "oi", tdt)), y=y,
@@ -93,7 +93,7 @@ def test_conv_dgrad(be, dt, N, H, W, Cin, Cout, stride, mode):
     xx = torch.zeros(N, Cin, H, W, requires_grad=True)
     ref_conv(xx, w.float(), stride).backward(dyt.float())
     ref = nhwc(xx.grad) + res.float()
-    dxo = torch.full((N, H, W, Cin), float("nan")).to(tdt).to(be.device)
+    dxo = be.out((N, H, W, Cin), tdt, float("nan"))
     wp = be.t(pack(w, "io", tdt)); dyd = be.t(nhwc(dyt)); rd = be.t(res)
     common = dict(dtype=code, N=N, IH=OH, IW=OW, Cin=Cout, OH=H, OW=W, Cout=Cin, wtaps=9, x=dyd, w=wp, y=dxo,
                   pro=cabi.pro(0), residual=rd, stats=None)
@@ -127,7 +127,7 @@ def test_conv_fwd_output_transform(be, dt, N, H, W, Cin, Cout, stride, emode, re
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
     dy, dx, wi = geo.taps_fwd(pt, pl)
     r = torch.randn(N, OH, OW, Cout, generator=g).to(tdt) if res else None
-    y = torch.full((N, OH, OW, Cout), float("nan")).to(tdt).to(be.device)
+    y = be.out((N, OH, OW, Cout), tdt, float("nan"))
     be.call("conv_fwd", cabi.make("mds_conv_fwd_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=OH, OW=OW, Cout=Cout, A=OH, B=OW,
                                   oy0=0, ox0=0, os=1, **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=be.t(nhwc(x)),
                                   w=be.t(pack(w, "oi", tdt)), y=y, pro=cabi.pro(0), residual=be.t(r) if res else None, stats=None,
@@ -160,7 +160,7 @@ def test_conv_dgrad_s2_tap_groups(be, dt, N, H, W, Cin, Cout, blocks):
     xx = torch.zeros(N, Cin, H, W, requires_grad=True)
     ref_conv(xx, w.float(), 2).backward(dyt.float())
     ref = nhwc(xx.grad)
-    dxo = torch.full((N, H, W, Cin), float("nan")).to(tdt).to(be.device)
+    dxo = be.out((N, H, W, Cin), tdt, float("nan"))
     par = []
     for py in range(2):
         for px in range(2):
@@ -212,7 +212,7 @@ def test_conv_wgrad(be, dt, N, H, W, Cin, Cout, stride, mode):
     ww = torch.zeros(Cout, Cin, 3, 3, requires_grad=True)
     ref_conv(a, ww, stride).backward(dyt.float())
     dy, dx, wi = geo.taps_fwd(pt, pl)
-    dw = torch.zeros(Cout, Cin, 3, 3, device=be.device)
+    dw = be.out((Cout, Cin, 3, 3), torch.float32, 0, name="dw")
     be.call("conv_wgrad", cabi.make("mds_conv_wgrad_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=OH, OW=OW,
                                     Cout=Cout, **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9,
                                     x=be.t(nhwc(x)), dyt=be.t(nhwc(dyt)), dw=dw,
@@ -246,8 +246,8 @@ def test_c3_filter_in_registers(be, N, H, W, Cin, Cout, res, stats, blocks):
     w = (torch.randn(Cout, Cin, 3, 3, generator=g) / (9 * Cin) ** 0.5).to(tdt)
     r = torch.randn(N, H, W, Cout, generator=g).to(tdt) if res else None
     dy, dx, wi = geo.taps_fwd(1, 1)
-    y = torch.full((N, H, W, Cout), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, Cout, device=be.device, dtype=torch.float64) if stats else None
+    y = be.out((N, H, W, Cout), tdt, float("nan"))
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, Cout), torch.float64, 0) if stats else None
     args = cabi.make("mds_conv_fwd_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=H, OW=W, Cout=Cout, A=H, B=W, oy0=0, ox0=0, os=1,
                      **{"is": 1}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=be.t(nhwc(x)), w=be.t(pack(w, "oi", tdt)), y=y,
                      pro=cabi.pro(0), residual=be.t(r) if res else None, stats=st)
@@ -315,8 +315,8 @@ def test_c3_post_statistics(be, stride, N, H, W, blocks, masked, Cin, Cout):
         xx = torch.zeros(N, Cin, H, W, requires_grad=True)
         ref_conv(xx, w.float(), stride).backward(dyt.float())
         ref = nhwc(xx.grad) + (res.float() if res is not None else 0)
-        dxo = torch.full((N, H, W, Cin), float("nan")).to(tdt).to(be.device)
-        st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, Cin, device=be.device, dtype=torch.float64)
+        dxo = be.out((N, H, W, Cin), tdt, float("nan"))
+        st = be.out((cabi.MDS_STAT_SLOTS, 2, Cin), torch.float64, 0)
         post = cabi.make("mds_poststat_t", mode=3 if silu else (2 if masked else 1), y=be.t(yb), bn=be.t(bn), mask=be.t(mask) if masked else None,
                          rows_per_group=H * W, stats=st)
         common = dict(dtype=code, N=N, IH=OH, IW=OW, Cin=Cout, OH=H, OW=W, Cout=Cin, wtaps=9, x=be.t(nhwc(dyt)), w=be.t(pack(w, "io", tdt)),
@@ -371,11 +371,11 @@ def test_conv_dgrad_post_ok_matches_the_launch(be, knob, dt, res, H, W, Cin, Cou
     code, tdt = DT[dt]                        # (Cin, Cout: the forward layer)
     N = 1
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, Cin, device=be.device, dtype=torch.float64)
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, Cin), torch.float64, 0)
     bn = torch.stack([torch.ones(Cin), torch.zeros(Cin), torch.zeros(Cin), torch.ones(Cin)])
     post = cabi.make("mds_poststat_t", mode=1, y=be.t(torch.zeros(N, H, W, Cin).to(tdt)), bn=be.t(bn), mask=None, rows_per_group=H * W, stats=st)
     common = dict(dtype=code, N=N, IH=OH, IW=OW, Cin=Cout, OH=H, OW=W, Cout=Cin, wtaps=9, x=be.t(torch.randn(N, OH, OW, Cout).to(tdt)),
-                  w=be.t(torch.randn(Cin, 9, Cout).to(tdt)), y=be.t(torch.zeros(N, H, W, Cin).to(tdt)), pro=cabi.pro(0),
+                  w=be.t(torch.randn(Cin, 9, Cout).to(tdt)), y=be.out((N, H, W, Cin), tdt, 0), pro=cabi.pro(0),
                   residual=be.t(torch.zeros(N, H, W, Cin).to(tdt)) if res else None, stats=None, post=post)
     if stride == 1:
         dy, dx, wi = geo.taps_dgrad_s1()
@@ -507,23 +507,23 @@ def test_k_c3_at_the_training_sizes_against_k_conv(be_gpu, H, W, Cin, Cout, stri
     be, N = be_gpu, int(os.environ.get("MDS_TEST_IMAGES", "20"))      # (20 = batch 4; 5 / 10 / 15 - other item and block counts - were run by hand: profiles/r06_other_batch_sizes.txt)
     code, tdt = DT["bf16"]
     g = torch.Generator(device=be.device).manual_seed(H + Cin + stride)
-    x = torch.randn(N, H, W, Cin, device=be.device, generator=g).to(tdt)
+    x = be.t(torch.randn(N, H, W, Cin, device=be.device, generator=g).to(tdt))
     w = (torch.randn(Cout, Cin, 3, 3, device=be.device, generator=g) / (9 * Cin) ** 0.5).to(tdt)
-    scale = 1 + 0.2 * torch.randn(Cin, device=be.device, generator=g); shift = 0.3 * torch.randn(Cin, device=be.device, generator=g)
+    scale = be.t(1 + 0.2 * torch.randn(Cin, device=be.device, generator=g)); shift = be.t(0.3 * torch.randn(Cin, device=be.device, generator=g))
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
-    dyt = torch.randn(N, OH, OW, Cout, device=be.device, generator=g).to(tdt)
+    dyt = be.t(torch.randn(N, OH, OW, Cout, device=be.device, generator=g).to(tdt))
     dy, dx, wi = geo.taps_fwd(pt, pl)
     wp = be.t(pack(w.cpu(), "oi", tdt))
     out = {}
     for knob in (0, 1):
         be.lib.check(be.lib.fn["dev_set"](cabi.MDS_KNOB_C3, knob), "dev_set")
         try:
-            y = torch.full((N, OH, OW, Cout), float("nan"), device=be.device).to(tdt)
-            st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, Cout, device=be.device, dtype=torch.float64)
+            y = be.out((N, OH, OW, Cout), tdt, float("nan"))
+            st = be.out((cabi.MDS_STAT_SLOTS, 2, Cout), torch.float64, 0)
             be.call("conv_fwd", cabi.make("mds_conv_fwd_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=OH, OW=OW, Cout=Cout, A=OH, B=OW,
                                           oy0=0, ox0=0, os=1, **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=x, w=wp, y=y,
                                           pro=cabi.pro(mode, scale, shift), residual=None, stats=st))
-            dw = torch.zeros(Cout, Cin, 3, 3, device=be.device)
+            dw = be.out((Cout, Cin, 3, 3), torch.float32, 0, name="dw")
             be.call("conv_wgrad", cabi.make("mds_conv_wgrad_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=OH, OW=OW, Cout=Cout,
                                             **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=x, dyt=dyt, dw=dw,
                                             pro=cabi.pro(mode, scale, shift)))

@@ -66,7 +66,7 @@ def project_struct(be, d, cout=None, w=True):
 
 
 def run_fused(be, d, emode=2):
-    y = torch.full((d["N"], d["OH"], d["OW"], d["cout"]), float("nan")).to(d["tdt"]).to(be.device)   # an unwritten pixel or channel stays NaN
+    y = be.out((d["N"], d["OH"], d["OW"], d["cout"]), d["tdt"], float("nan"))   # an unwritten pixel or channel stays NaN
     res = be.t(d["res"], d["tdt"]) if d["res"] is not None else None
     be.call("conv_fwd", cabi.make("mds_conv_fwd_args", **conv_args(be, d, emode, y, d["cout"], residual=res, project=project_struct(be, d))))
     be.sync()
@@ -76,9 +76,9 @@ def run_fused(be, d, emode=2):
 def run_unfused(be, d, emode=2):
     """the two launches of an inference plan without the switch"""
     M = d["N"] * d["OH"] * d["OW"]
-    ya = torch.full((d["N"], d["OH"], d["OW"], d["mid"]), float("nan")).to(d["tdt"]).to(be.device)
+    ya = be.out((d["N"], d["OH"], d["OW"], d["mid"]), d["tdt"], float("nan"))
     be.call("conv_fwd", cabi.make("mds_conv_fwd_args", **conv_args(be, d, emode, ya, d["mid"])))
-    y = torch.full((d["N"], d["OH"], d["OW"], d["cout"]), float("nan")).to(d["tdt"]).to(be.device)
+    y = be.out((d["N"], d["OH"], d["OW"], d["cout"]), d["tdt"], float("nan"))
     res = be.t(d["res"], d["tdt"]) if d["res"] is not None else None
     be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=d["code"], M=M, K=d["mid"], N=d["cout"], x=ya, w=be.t(d["w2"], d["tdt"]), y=y,
                                 pro=cabi.pro(0), residual=res, stats=None,
@@ -147,7 +147,7 @@ def test_conv_project_null_is_the_plain_launch(be):
         d = build(dt, 1, 9, 13, 32, 128, 32, 1, False, seed=6)
         ys = []
         for extra in ({}, dict(project=project_struct(be, d, w=False))):
-            y = torch.full((1, d["OH"], d["OW"], d["mid"]), float("nan")).to(d["tdt"]).to(be.device)
+            y = be.out((1, d["OH"], d["OW"], d["mid"]), d["tdt"], float("nan"))
             be.call("conv_fwd", cabi.make("mds_conv_fwd_args", **conv_args(be, d, 2, y, d["mid"], **extra)))
             be.sync()
             ys.append(y.cpu())
@@ -158,15 +158,15 @@ def test_conv_project_rejects_unsupported(be):
     """statistics, a prologue, tap groups, os == 2, a width off the 16-grid or beyond a published limit: errors, never a
     silent two-launch fallback"""
     d = build("f32", 1, 8, 8, 32, 128, 32, 1, False)
-    z = lambda n: torch.zeros(n, device=be.device)
+    z = lambda n: be.out(n, torch.float32, 0)
     y = z(64 * 128)
 
     def rc(dd=d, **extra):
         a = cabi.make("mds_conv_fwd_args", **{**conv_args(be, dd, 2, y, dd["cout"], project=project_struct(be, dd)), **extra})
-        return be.lib.fn["conv_fwd"](cabi.C.byref(a), be.stream())
+        return be.rc("conv_fwd", a)
 
     assert rc() == 0                                                         # the base case itself is legal
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, 128, dtype=torch.float64, device=be.device)
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, 128), torch.float64, 0)
     assert rc(stats=st) == cabi.MDS_ERR_BAD_ARG
     assert rc(epi=cabi.make("mds_epi_t", mode=0, scale=None, shift=None)) == cabi.MDS_ERR_BAD_ARG
     assert rc(pro=cabi.pro(2, z(32), z(32))) == cabi.MDS_ERR_BAD_ARG
@@ -181,6 +181,7 @@ def test_conv_project_rejects_unsupported(be):
     deep = build("f32", 1, 8, 8, 16, cabi.MDS_PROJECT_MID_MAX + 16, 32, 1, False)
     assert rc(deep) == cabi.MDS_ERR_BAD_ARG
     assert b"project" in be.lib.dll.mds_last_error()
+    be.sync()
 
 
 # the four blocks at their sizes in the 736 x 1280 encoder

@@ -27,8 +27,8 @@ def run_case(be, dt, N, H, W, cin, mid, stride, shift1=0.3, emode=2, pool=True, 
     z = z * s2.view(1, -1, 1, 1) + b2.view(1, -1, 1, 1)
     ref = F.silu(z) if emode == 2 else z
     ref = ref.permute(0, 2, 3, 1).contiguous()
-    y = torch.full((N, OH, OW, mid), float("nan")).to(tdt).to(be.device)
-    pooled = torch.zeros(N, mid, dtype=torch.float64, device=be.device)
+    y = be.out((N, OH, OW, mid), tdt, float("nan"))
+    pooled = be.out((N, mid), torch.float64, 0)
     exp = cabi.make("mds_expand_t", x=be.t(x.permute(0, 2, 3, 1), tdt), w=be.t(w1, tdt), cin=cin, scale=be.t(s1), shift=be.t(b1))
     be.call("dw_fwd", cabi.make("mds_dw_fwd_args", dtype=code, N=N, T=1, IH=H, IW=W, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt,
                                 pad_l=pl, kt=1, x=None, w=be.t(wd.view(mid, 9)), y=y, pro=cabi.pro(0), stats=None,
@@ -77,14 +77,14 @@ def test_dw_fwd_expand_affine_output(be):
 def test_dw_fwd_expand_rejects_unsupported(be):
     """3D, a prologue or statistics with the expansion are errors, not silent fallbacks"""
     code, tdt = DT["f32"]
-    z = lambda n: torch.zeros(n, device=be.device)
+    z = lambda n: be.out(n, torch.float32, 0)
     exp = cabi.make("mds_expand_t", x=z(2 * 4 * 4 * 48), w=z(192 * 48), cin=48, scale=z(192), shift=z(192))
     epi = cabi.make("mds_epi_t", mode=2, scale=z(192), shift=z(192))
     base = dict(dtype=code, N=1, IH=4, IW=4, C=192, OH=4, OW=4, stride=1, pad_t=1, pad_l=1, x=None, w=z(192 * 27), y=z(16 * 192),
                 stats=None, epi=epi, pool=None, pool_inv=0.0, expand=exp)
     for bad in (dict(T=2, kt=3, pro=cabi.pro(0)), dict(T=1, kt=1, pro=cabi.pro(2, z(192), z(192)))):
         a = cabi.make("mds_dw_fwd_args", **{**base, **bad})
-        rc = be.lib.fn["dw_fwd"](cabi.C.byref(a), be.stream())
+        rc = be.rc("dw_fwd", a)
         assert rc == cabi.MDS_ERR_BAD_ARG
 
 

@@ -60,12 +60,12 @@ def build(be, dt, N, H, W, mid, R, stride, kt, cin, seed=0):
 
 def launch(be, kw, shape, se=None, ticket=None):
     N, T, OH, OW, mid, tdt = shape
-    y = torch.full((N, T, OH, OW, mid), UNWRITTEN).to(tdt).to(be.device)
-    pooled = torch.zeros(N, mid, dtype=torch.float64, device=be.device)
+    y = be.out((N, T, OH, OW, mid), tdt, UNWRITTEN)
+    pooled = be.out((N, mid), torch.float64, 0)
     out = {}
     extra = {}
     if se is not None:
-        out = dict(hidden=torch.full((N, se["R"]), UNWRITTEN, device=be.device), gate=torch.full((N, mid), UNWRITTEN, device=be.device))
+        out = dict(hidden=be.out((N, se["R"]), torch.float32, UNWRITTEN), gate=be.out((N, mid), torch.float32, UNWRITTEN))
         extra["se"] = cabi.make("mds_se_tail_t", R=se["R"], w1=se["w1"], b1=se["b1"], w2t=se["w2t"], b2=se["b2"], ticket=ticket, **out)
     be.call("dw_fwd", cabi.make("mds_dw_fwd_args", y=y, pool=pooled, **kw, **extra))
     be.sync()
@@ -74,8 +74,8 @@ def launch(be, kw, shape, se=None, ticket=None):
 
 def se_fc(be, se, pooled):
     N, mid = pooled.shape
-    hidden = torch.empty(N, se["R"], device=be.device)
-    gate = torch.empty(N, mid, device=be.device)
+    hidden = be.out((N, se["R"]), torch.float32, float("nan"))
+    gate = be.out((N, mid), torch.float32, float("nan"))
     be.call("se_fc_fwd", cabi.make("mds_se_fc_fwd_args", groups=N, C=mid, R=se["R"], pooled=pooled, w1=se["w1"], b1=se["b1"],
                                    w2=se["w2"], b2=se["b2"], hidden=hidden, gate=gate, w2t=se["w2t"]))
     be.sync()
@@ -108,7 +108,7 @@ CASES = [
 def test_tail_matches_se_fc_fwd(be, dt, N, H, W, mid, R, stride, kt, cin):
     kw, se, shape = build(be, dt, N, H, W, mid, R, stride, kt, cin)
     y0, p0, _, _ = launch(be, kw, shape)
-    ticket = torch.zeros(N, dtype=torch.int32, device=be.device)
+    ticket = be.out(N, torch.int32, 0)
     y1, p1, hidden, gate = launch(be, kw, shape, se, ticket)
     # the tail only adds work after y and pooled (fp64 sums: order-independent to 1e-16, and the flush order is the launch's own)
     bits = torch.int16 if dt == "bf16" else torch.int32
@@ -136,11 +136,11 @@ def test_tail_matches_se_fc_fwd(be, dt, N, H, W, mid, R, stride, kt, cin):
 def test_relaunch_gives_the_same_gate(be, N, H, W, mid, R, stride, kt, cin):
     """the same arguments three times on one stream, pooled re-zeroed between launches as the plan does: the ticket resets itself"""
     kw, se, shape = build(be, "f32", N, H, W, mid, R, stride, kt, cin, seed=3)
-    ticket = torch.zeros(N, dtype=torch.int32, device=be.device)
+    ticket = be.out(N, torch.int32, 0)
     _, T, OH, OW, _, tdt = shape
-    y = torch.empty((N, T, OH, OW, mid), dtype=tdt, device=be.device)
-    pooled = torch.zeros(N, mid, dtype=torch.float64, device=be.device)
-    hidden, gate = torch.empty(N, R, device=be.device), torch.empty(N, mid, device=be.device)
+    y = be.out((N, T, OH, OW, mid), tdt, float("nan"))
+    pooled = be.out((N, mid), torch.float64, 0)
+    hidden, gate = be.out((N, R), torch.float32, float("nan")), be.out((N, mid), torch.float32, float("nan"))
     args = cabi.make("mds_dw_fwd_args", y=y, pool=pooled, **kw,
                      se=cabi.make("mds_se_tail_t", R=R, w1=se["w1"], b1=se["b1"], w2t=se["w2t"], b2=se["b2"], hidden=hidden, gate=gate,
                                   ticket=ticket))
@@ -164,11 +164,11 @@ def test_unsupported_combinations_are_refused(be, cin):
     N, mid, R = 2, 192, 12
     kw, se, shape = build(be, "f32", N, 9, 13, mid, R, 1, 1, cin, seed=4)
     _, T, OH, OW, _, tdt = shape
-    y = torch.empty((N, T, OH, OW, mid), dtype=tdt, device=be.device)
-    pooled = torch.zeros(N, mid, dtype=torch.float64, device=be.device)
-    hidden, gate = torch.empty(N, R, device=be.device), torch.empty(N, mid, device=be.device)
-    ticket = torch.zeros(N, dtype=torch.int32, device=be.device)
-    pad = torch.zeros(R * mid + 4, device=be.device)
+    y = be.out((N, T, OH, OW, mid), tdt, float("nan"))
+    pooled = be.out((N, mid), torch.float64, 0)
+    hidden, gate = be.out((N, R), torch.float32, float("nan")), be.out((N, mid), torch.float32, float("nan"))
+    ticket = be.out(N, torch.int32, 0)
+    pad = be.out(R * mid + 4, torch.float32, 0)
 
     def tail(**over):
         f = dict(R=R, w1=se["w1"], b1=se["b1"], w2t=se["w2t"], b2=se["b2"], hidden=hidden, gate=gate, ticket=ticket)
@@ -178,7 +178,7 @@ def test_unsupported_combinations_are_refused(be, cin):
     def rc(se_struct, **over):
         k = dict(kw, y=y, pool=pooled)
         k.update(over)
-        code = be.lib.fn["dw_fwd"](ctypes.byref(cabi.make("mds_dw_fwd_args", se=se_struct, **k)), be.stream())
+        code = be.rc("dw_fwd", cabi.make("mds_dw_fwd_args", se=se_struct, **k))
         return code, be.lib.dll.mds_last_error().decode()
 
     bad = [
@@ -196,11 +196,11 @@ def test_unsupported_combinations_are_refused(be, cin):
     Cb = cabi.MDS_SE_TAIL_CMAX + 64
     if not cin:
         kwb, seb, shb = build(be, "f32", 1, 4, 8, Cb, 8, 1, 1, 0, seed=5)
-        yb = torch.empty((1, 1, 4, 8, Cb), device=be.device)
-        pb = torch.zeros(1, Cb, dtype=torch.float64, device=be.device)
-        t = cabi.make("mds_se_tail_t", R=8, w1=seb["w1"], b1=seb["b1"], w2t=seb["w2t"], b2=seb["b2"], hidden=torch.empty(1, 8, device=be.device),
-                      gate=torch.empty(1, Cb, device=be.device), ticket=ticket)
-        code = be.lib.fn["dw_fwd"](ctypes.byref(cabi.make("mds_dw_fwd_args", y=yb, pool=pb, se=t, **kwb)), be.stream())
+        yb = be.out((1, 1, 4, 8, Cb), torch.float32, float("nan"))
+        pb = be.out((1, Cb), torch.float64, 0)
+        t = cabi.make("mds_se_tail_t", R=8, w1=seb["w1"], b1=seb["b1"], w2t=seb["w2t"], b2=seb["b2"], hidden=be.out((1, 8), torch.float32, float("nan")),
+                      gate=be.out((1, Cb), torch.float32, float("nan")), ticket=ticket)
+        code = be.rc("dw_fwd", cabi.make("mds_dw_fwd_args", y=yb, pool=pb, se=t, **kwb))
         assert code < 0 and "C <=" in be.lib.dll.mds_last_error().decode()
     # 3D stacks other than T = 5 have no pooling kernel, with or without the tail
     code, msg = rc(tail(), kt=3, T=3) if not cin else (-1, "sliding-window")

@@ -99,8 +99,8 @@ def _dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt, rd=torch.float32):
     # forward kernel
     xd = be.t(to_rows(x)); wd = be.t(w.view(C, kt * 9))
     scd, shd = be.t(scale.float()), be.t(shift.float())
-    y = torch.full((N, T, OH, OW, C), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)
+    y = be.out((N, T, OH, OW, C), tdt, float("nan"))
+    st = be.out((SLOTS, 2, C), torch.float64, 0)
     pro = cabi.pro(2, scd, shd)
     be.call("dw_fwd", cabi.make("mds_dw_fwd_args", dtype=code, N=N, T=T, IH=H, IW=W, C=C, OH=OH, OW=OW, stride=stride,
                                 pad_t=pt, pad_l=pl, kt=kt, x=xd, w=wd, y=y, pro=pro, stats=st))
@@ -112,9 +112,9 @@ def _dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt, rd=torch.float32):
     assert_close(s[0], yr.sum((0, 1, 2, 3)), dt, scale=cnt ** 0.5, msg="sum")
     assert_close(s[1], (yr * yr).sum((0, 1, 2, 3)), dt, scale=cnt ** 0.5, msg="sumsq")
     # backward kernel
-    gout = torch.full((N, T, H, W, C), float("nan")).to(tdt).to(be.device)
-    dw = torch.zeros(C, kt * 9, device=be.device)
-    st2 = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)     # backward sums: fp64 slots
+    gout = be.out((N, T, H, W, C), tdt, float("nan"))
+    dw = be.out((C, kt * 9), torch.float32, 0, name="dw")
+    st2 = be.out((SLOTS, 2, C), torch.float64, 0)     # backward sums: fp64 slots
     be.call("dw_bwd", cabi.make("mds_dw_bwd_args", dtype=code, N=N, T=T, IH=H, IW=W, C=C, OH=OH, OW=OW, stride=stride,
                                 pad_t=pt, pad_l=pl, kt=kt, x=xd, dy=be.t(to_rows(dyt)), w=wd, g=gout, dw=dw, pro=pro,
                                 mean=be.t(mean.float()), rstd=be.t(rstd.float()), stats=st2))
@@ -141,9 +141,9 @@ def test_dw_fwd_output_transform(be, dt, N, T, H, W, C, stride, kt):
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
     pads = (geo.same_pad(H, stride), geo.same_pad(W, stride)) if stride == 2 else ((1, 1), (1, 1))
     ref = F.silu(dw_ref(x.float(), w, stride, kt, pads) * esc.view(1, -1, 1, 1, 1) + esh.view(1, -1, 1, 1, 1))
-    y = torch.full((N, T, OH, OW, C), float("nan")).to(tdt).to(be.device)
+    y = be.out((N, T, OH, OW, C), tdt, float("nan"))
     # (kt == 1: T == 1 in every case; the pooled means of the STORED output come out of the same pass - mds_dw_fwd_args.pool)
-    pool = torch.zeros(N, C, dtype=torch.float64, device=be.device)
+    pool = be.out((N, C), torch.float64, 0)
     be.call("dw_fwd", cabi.make("mds_dw_fwd_args", dtype=code, N=N, T=T, IH=H, IW=W, C=C, OH=OH, OW=OW, stride=stride, pad_t=pt,
                                 pad_l=pl, kt=kt, x=be.t(to_rows(x)), w=be.t(w.view(C, kt * 9)), y=y, pro=cabi.pro(0), stats=None,
                                 epi=cabi.make("mds_epi_t", mode=2, scale=be.t(esc), shift=be.t(esh)),
@@ -170,12 +170,12 @@ def test_stem_fwd_wgrad(be, dt, N, H, W, rd=torch.float32):
     dyt = torch.randn(yref.shape, generator=g).to(tdt)
     yref.backward(dyt.to(rd))
     wp = torch.zeros(32, 32); wp[:, :27] = w.view(32, 27)
-    y = torch.full((N, OH, OW, 32), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(SLOTS, 2, 32, device=be.device, dtype=torch.float64)
+    y = be.out((N, OH, OW, 32), tdt, float("nan"))
+    st = be.out((SLOTS, 2, 32), torch.float64, 0)
     xd = be.t(x)
     be.call("stem_fwd", cabi.make("mds_stem_fwd_args", dtype=code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
                                   x=xd, w=be.t(wp.to(tdt)), y=y, stats=st))
-    dw = torch.zeros(32, 3, 3, 3, device=be.device)
+    dw = be.out((32, 3, 3, 3), torch.float32, 0, name="dw")
     be.call("stem_wgrad", cabi.make("mds_stem_wgrad_args", dtype=code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt,
                                     pad_l=pl, x=xd, dy=be.t(dyt.permute(0, 2, 3, 1)), dw=dw))
     be.sync()
@@ -200,7 +200,7 @@ def test_stem_fwd_output_transform(be, dt):
     (pt_, pb), (pl_, pr) = geo.same_pad(H, 2), geo.same_pad(W, 2)
     ref = F.silu(F.conv2d(F.pad(x.to(tdt).float(), (pl_, pr, pt_, pb)), w.to(tdt).float(), None, 2).permute(0, 2, 3, 1) * esc + esh)
     wp = torch.zeros(32, 32); wp[:, :27] = w.view(32, 27)
-    y = torch.full((N, OH, OW, 32), float("nan")).to(tdt).to(be.device)
+    y = be.out((N, OH, OW, 32), tdt, float("nan"))
     be.call("stem_fwd", cabi.make("mds_stem_fwd_args", dtype=code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
                                   x=be.t(x), w=be.t(wp.to(tdt)), y=y, stats=None,
                                   epi=cabi.make("mds_epi_t", mode=2, scale=be.t(esc), shift=be.t(esh))))
@@ -228,7 +228,7 @@ def test_stem_wgrad_forms_dy_on_load(be, gmode, N, H, W):
     xd = be.t(x)
     out = []
     for fused in (False, True):
-        dw = torch.zeros(32, 3, 3, 3, device=be.device)
+        dw = be.out((32, 3, 3, 3), torch.float32, 0, name="dw")
         kw = dict(dtype=code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl, x=xd, dw=dw)
         if fused:
             kw.update(dy=None, dyp=cabi.make("mds_dyp_t", mode=1, g=cabi.gsrc(gmode, be.t(u)), y=be.t(y), bn=be.t(bn), lin=be.t(lin)))
@@ -258,7 +258,7 @@ def test_stem_fwd_uint8_ingest(be, dt):
     (pt_, pb), (pl_, pr) = geo.same_pad(H, 2), geo.same_pad(W, 2)
     yref = F.conv2d(F.pad(x.to(tdt).float(), (pl_, pr, pt_, pb)), w.to(tdt).float(), None, 2).permute(0, 2, 3, 1)
     wp = torch.zeros(32, 32); wp[:, :27] = w.view(32, 27)
-    y = torch.full((N, OH, OW, 32), float("nan")).to(tdt).to(be.device)
+    y = be.out((N, OH, OW, 32), tdt, float("nan"))
     ing = cabi.make("mds_ingest_t", u8=be.t(u8), nsrc=nsrc, src_h=sh, src_w=sw, pad_top=hp // 2, pad_left=wp_ // 2, scale=1.0 / 255.0)
     be.call("stem_fwd", cabi.make("mds_stem_fwd_args", dtype=code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
                                   x=None, w=be.t(wp.to(tdt)), y=y, stats=None, ingest=ing))

@@ -15,7 +15,7 @@ def gen(s):
 
 def bn_finalize(be, stats, count, gamma, beta, eps=1e-3, momentum=0.1, training=1, rm=None, rv=None, nbt=None):
     C = gamma.numel()
-    out = torch.empty(4, C, device=be.device)
+    out = be.out((4, C), torch.float32, float("nan"))
     be.call("bn_finalize", cabi.make("mds_bn_finalize_args", C=C, count=count, stats=stats, gamma=gamma,
                                      beta=beta, eps=eps, momentum=momentum, training=training,
                                      running_mean=rm, running_var=rv, num_batches_tracked=nbt, out=out))
@@ -56,9 +56,9 @@ def test_bn_res(be, dt, M, C, act, use_mask, use_sc):
     y = torch.randn(M, C, generator=g).to(tdt); sc_ = torch.randn(M, C, generator=g).to(tdt)
     scale = 1 + 0.2 * torch.randn(C, generator=g); shift = 0.2 * torch.randn(C, generator=g)
     mask = (torch.rand((M + rpg - 1) // rpg, generator=g) > 0.3).float() / 0.7
-    out = torch.empty(M, C, dtype=tdt, device=be.device)
+    out = be.out((M, C), tdt, float("nan"))
     be.call("bn_res", cabi.make("mds_bn_res_args", dtype=code, M=M, C=C, y=be.t(y), scale=be.t(scale),
-                                shift=be.t(shift), act=act, mask=be.t(mask) if use_mask else None,
+                                shift=be.t(shift), act=act, mask=be.t(mask, name="mask") if use_mask else None,
                                 rows_per_group=rpg, shortcut=be.t(sc_) if use_sc else None, out=out))
     be.sync()
     z = y.float() * scale + shift
@@ -98,30 +98,30 @@ def test_se_forward_backward(be, dt, packed, C, RD):
     (out * u.float().view(G, R_, C)).sum().backward()
     # kernels
     yd = be.t(y); ud = be.t(u); scd = be.t(scale); shd = be.t(shift)
-    pooled = torch.zeros(G, C, device=be.device, dtype=torch.float64)      # cross-block sums that feed activations: fp64
+    pooled = be.out((G, C), torch.float64, 0)      # cross-block sums that feed activations: fp64
     be.call("se_pool", cabi.make("mds_se_pool_args", dtype=code, groups=G, rows_per_group=R_, C=C, y=yd,
                                  scale=scd, shift=shd, pooled=pooled))
-    hidden = torch.empty(G, RD, device=be.device); gate = torch.empty(G, C, device=be.device)
+    hidden = be.out((G, RD), torch.float32, float("nan")); gate = be.out((G, C), torch.float32, float("nan"))
     w1d, b1d, w2d, b2d = be.t(w1), be.t(b1), be.t(w2), be.t(b2)
     w2t = None
     if packed:
-        w2t = torch.full((RD, C), float("nan"), device=be.device)
+        w2t = be.out((RD, C), torch.float32, float("nan"))
         job = cabi.make("mds_pack_job", src=w2d, dst=w2t, kind=cabi.MDS_PACK_IO_F32, O=C, I=RD, taps=1)
-        raw = torch.frombuffer(bytearray(bytes(job)), dtype=torch.uint8).to(be.device)
-        be.lib.check(be.lib.fn["pack_weights"](raw.data_ptr(), 1, C * RD, code, be.stream()), "pack_weights")
+        raw = be.t(torch.frombuffer(bytearray(bytes(job)), dtype=torch.uint8))
+        be.lib.check(be.lib.fn["pack_weights"](be.ptr(raw), 1, C * RD, code, be.stream()), "pack_weights")
         be.sync()
         assert torch.equal(w2t.cpu(), w2.t().contiguous())
     be.call("se_fc_fwd", cabi.make("mds_se_fc_fwd_args", groups=G, C=C, R=RD, pooled=pooled, w1=w1d, b1=b1d,
                                    w2=w2d, b2=b2d, hidden=hidden, gate=gate, w2t=w2t))
-    dgate = torch.zeros(G, C, device=be.device, dtype=torch.float64)
+    dgate = be.out((G, C), torch.float64, 0)
     be.call("se_bwd_reduce", cabi.make("mds_se_bwd_reduce_args", dtype=code, groups=G, rows_per_group=R_, C=C,
                                        u=ud, y=yd, scale=scd, shift=shd, dgate=dgate))
-    dpooled = torch.empty(G, C, device=be.device)
-    dw1 = torch.zeros(RD, C, device=be.device); db1 = torch.zeros(RD, device=be.device)
-    dw2 = torch.zeros(C, RD, device=be.device); db2 = torch.zeros(C, device=be.device)
+    dpooled = be.out((G, C), torch.float32, float("nan"))
+    dw1 = be.out((RD, C), torch.float32, 0); db1 = be.out(RD, torch.float32, 0)
+    dw2 = be.out((C, RD), torch.float32, 0); db2 = be.out(C, torch.float32, 0)
     be.call("se_fc_bwd", cabi.make("mds_se_fc_bwd_args", groups=G, C=C, R=RD, rows_per_group=R_, dgate=dgate,
                                    gate=gate, hidden=hidden, pooled=pooled, w1=w1d, w2=w2d, dpooled=dpooled,
-                                   scratch=torch.empty(G, RD, device=be.device), dw1=dw1, db1=db1, dw2=dw2, db2=db2,
+                                   scratch=be.out((G, RD), torch.float32, float("nan")), dw1=dw1, db1=db1, dw2=dw2, db2=db2,
                                    w2t=w2t))
     be.sync()
     assert_close(pooled, pooled_ref, dt, msg="pooled")
@@ -149,14 +149,14 @@ def test_se_parameter_gradients_table_equals_the_per_layer_launches(be):
         init = [torch.randn(R, C, generator=g), torch.randn(R, generator=g), torch.randn(C, R, generator=g), torch.randn(C, generator=g)]
         two = []
         for _ in range(2):
-            gr = [be.t(t.clone()) for t in init]
+            gr = [be.out(t.shape, torch.float32, t, name=n) for t, n in zip(init, ("dw1", "db1", "dw2", "db2"))]
             two.append((gr, cabi.make("mds_se_fc_bwd_args", groups=G, C=C, R=R, rows_per_group=70, dgate=dgate, gate=gate, hidden=hidden,
-                                      pooled=pooled, w1=w1, w2=w2, dpooled=torch.empty(G, C, device=be.device), scratch=scratch,
+                                      pooled=pooled, w1=w1, w2=w2, dpooled=be.out((G, C), torch.float32, float("nan")), scratch=scratch,
                                       dw1=gr[0], db1=gr[1], dw2=gr[2], db2=gr[3])))
         be.call("se_fc_bwd_params", two[0][1])
         jobs.append(two[1][1]); outs.append((two[0][0], two[1][0]))
     arr = (SJ * len(jobs))(*jobs)
-    tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(be.device)
+    tab = be.t(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8))
     be.call("se_fc_bwd_params_table", cabi.make("mds_se_fc_bwd_table_args", jobs=tab, njobs=len(jobs), max_rc=max(C * R for C, R in shapes)))
     be.sync()
     for (C, R), (ref, got) in zip(shapes, outs):
@@ -198,15 +198,15 @@ def test_bn_backward_chain(be, dt, mode, C):
     stats = torch.zeros(SLOTS, 2, C, dtype=torch.float64)
     stats[0, 0] = y.float().sum(0); stats[0, 1] = (y.float() ** 2).sum(0)
     bn = bn_finalize(be, be.t(stats), M, be.t(gamma), be.t(beta), eps=eps)
-    gs = cabi.gsrc(mode, be.t(u), be.t(gate), be.t(dpool), be.t(mask), rpg)
-    st2 = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)     # backward sums: fp64 slots
+    gs = cabi.gsrc(mode, be.t(u), be.t(gate), be.t(dpool), be.t(mask, name="mask"), rpg)
+    st2 = be.out((SLOTS, 2, C), torch.float64, 0)     # backward sums: fp64 slots
     yd = be.t(y)
     be.call("bn_bwd_reduce", cabi.make("mds_bn_bwd_reduce_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, stats=st2))
-    dgamma = torch.zeros(C, device=be.device); dbeta = torch.zeros(C, device=be.device)
-    coef = torch.empty(3, C, device=be.device)
+    dgamma = be.out(C, torch.float32, 0, name="dgamma"); dbeta = be.out(C, torch.float32, 0, name="dbeta")
+    coef = be.out((3, C), torch.float32, float("nan"))
     be.call("bn_bwd_finalize", cabi.make("mds_bn_bwd_finalize_args", C=C, count=M, stats=st2, gamma=be.t(gamma),
                                          bn=bn, dgamma=dgamma, dbeta=dbeta, coef=coef, batch_stats=1))
-    dy = torch.empty(M, C, dtype=tdt, device=be.device)
+    dy = be.out((M, C), tdt, float("nan"))
     be.call("bn_bwd_apply", cabi.make("mds_bn_bwd_apply_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, coef=coef, dy=dy))
     be.sync()
     assert_close(dgamma, gam.grad, dt, scale=20, msg="dgamma")
@@ -252,16 +252,16 @@ def _bn_bwd_chain(be, dt, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, 
         bn = bn_finalize(be, None, 0, be.t(gamma), be.t(beta), eps=eps, training=0, rm=be.t(running[0]), rv=be.t(running[1]))
     gs = cabi.gsrc(mode, be.t(u), be.t(gate) if gate is not None else None, be.t(dpool) if dpool is not None else None,
                    be.t(mask) if mask is not None else None, rpg)
-    st2 = torch.zeros(SLOTS, 2, C, device=be.device, dtype=torch.float64)
+    st2 = be.out((SLOTS, 2, C), torch.float64, 0)
     yd = be.t(y)
     be.call("bn_bwd_reduce", cabi.make("mds_bn_bwd_reduce_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, stats=st2))
-    dgamma = torch.zeros(C, device=be.device); dbeta = torch.zeros(C, device=be.device)
-    coef = torch.full((3, C), float("nan"), device=be.device); lin = torch.full((3, C), float("nan"), device=be.device)
-    coef64 = torch.full((3, C), float("nan"), device=be.device, dtype=torch.float64) if use64 else None
+    dgamma = be.out(C, torch.float32, 0, name="dgamma"); dbeta = be.out(C, torch.float32, 0, name="dbeta")
+    coef = be.out((3, C), torch.float32, float("nan")); lin = be.out((3, C), torch.float32, float("nan"))
+    coef64 = be.out((3, C), torch.float64, float("nan")) if use64 else None
     be.call("bn_bwd_finalize", cabi.make("mds_bn_bwd_finalize_args", C=C, count=M, stats=st2, gamma=be.t(gamma), bn=bn, dgamma=dgamma,
                                          dbeta=dbeta, coef=coef, lin=lin, batch_stats=0 if running is not None else 1,
                                          fwd_stats=fwd if use64 else None, coef64=coef64))
-    dy = torch.full((M, C), float("nan")).to(tdt).to(be.device)
+    dy = be.out((M, C), tdt, float("nan"))
     be.call("bn_bwd_apply", cabi.make("mds_bn_bwd_apply_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, coef=coef, dy=dy, coef64=coef64))
     be.sync()
     return dy, dgamma, dbeta, coef, lin
@@ -351,12 +351,12 @@ def test_gem_fwd_bwd(be, dt, pro_mode, split, R_, C, golden):
     (pooled_ref * dpo).sum().backward()
     yd = be.t(y)
     pro = cabi.pro(pro_mode, be.t(scale), be.t(shift))
-    pooled = torch.empty(G, C, device=be.device); pd = be.t(p)
-    acc1 = torch.zeros(G, C, device=be.device, dtype=torch.float64) if split else None
-    acc2 = torch.zeros(G, C, device=be.device, dtype=torch.float64) if split else None
+    pooled = be.out((G, C), torch.float32, float("nan")); pd = be.t(p)
+    acc1 = be.out((G, C), torch.float64, 0) if split else None
+    acc2 = be.out((G, C), torch.float64, 0) if split else None
     be.call("gem_fwd", cabi.make("mds_gem_fwd_args", dtype=code, groups=G, rows_per_group=R_, C=C, y=yd, pro=pro,
                                  p=pd, eps=1e-6, pooled=pooled, accum=acc1))
-    u = torch.empty(G * R_, C, dtype=tdt, device=be.device); dp = torch.zeros(1, device=be.device)
+    u = be.out((G * R_, C), tdt, float("nan")); dp = be.out(1, torch.float32, 0, name="dp")
     be.call("gem_bwd", cabi.make("mds_gem_bwd_args", dtype=code, groups=G, rows_per_group=R_, C=C, y=yd, pro=pro,
                                  p=pd, eps=1e-6, pooled=pooled, dpooled=be.t(dpo), u=u, dp=dp, accum=acc2))
     be.sync()
@@ -374,12 +374,12 @@ def test_gem_matches_reference_golden(be, golden):
     rows = torch.zeros(B * H * W, Cp)
     rows[:, :C] = x.permute(0, 2, 3, 1).reshape(-1, C)
     rows[:, C:] = 1.0
-    pooled = torch.empty(B, Cp, device=be.device); p = be.t(torch.tensor([3.0]))
+    pooled = be.out((B, Cp), torch.float32, float("nan")); p = be.t(torch.tensor([3.0]))
     yd = be.t(rows)
     be.call("gem_fwd", cabi.make("mds_gem_fwd_args", dtype=0, groups=B, rows_per_group=H * W, C=Cp, y=yd,
                                  pro=cabi.pro(0), p=p, eps=1e-6, pooled=pooled))
     dpo = torch.zeros(B, Cp); dpo[:, :C] = torch.from_numpy(d["g"])
-    u = torch.empty(B * H * W, Cp, device=be.device); dp = torch.zeros(1, device=be.device)
+    u = be.out((B * H * W, Cp), torch.float32, float("nan")); dp = be.out(1, torch.float32, 0, name="dp")
     be.call("gem_bwd", cabi.make("mds_gem_bwd_args", dtype=0, groups=B, rows_per_group=H * W, C=Cp, y=yd,
                                  pro=cabi.pro(0), p=p, eps=1e-6, pooled=pooled, dpooled=be.t(dpo), u=u, dp=dp))
     be.sync()
@@ -398,10 +398,10 @@ def test_head_fwd_bwd(be):
     pf = pooled.clone().requires_grad_(True); wf = w.clone().requires_grad_(True); bf = b.clone().requires_grad_(True)
     ref = F.linear(pf * mask, wf, bf)
     ref.backward(dl)
-    logits = torch.empty(B, NC, device=be.device)
-    pd, md, wd = be.t(pooled), be.t(mask), be.t(w)
+    logits = be.out((B, NC), torch.float32, float("nan"))
+    pd, md, wd = be.t(pooled), be.t(mask, name="mask"), be.t(w)
     be.call("head_fwd", cabi.make("mds_head_fwd_args", B=B, F=Fdim, NC=NC, pooled=pd, mask=md, w=wd, b=be.t(b), logits=logits))
-    dpo = torch.empty(B, Fdim, device=be.device); dw = torch.zeros(NC, Fdim, device=be.device); db = torch.zeros(NC, device=be.device)
+    dpo = be.out((B, Fdim), torch.float32, float("nan")); dw = be.out((NC, Fdim), torch.float32, 0, name="dw"); db = be.out(NC, torch.float32, 0, name="db")
     be.call("head_bwd", cabi.make("mds_head_bwd_args", B=B, F=Fdim, NC=NC, pooled=pd, mask=md, w=wd, dlogits=be.t(dl),
                                   dpooled=dpo, dw=dw, db=db))
     be.sync()
@@ -416,7 +416,7 @@ def test_head_fwd_probs(be, tta):
     g = gen(32 + tta)
     pooled = torch.randn(B, Fdim, generator=g); w = torch.randn(NC, Fdim, generator=g) * 0.1; b = torch.randn(NC, generator=g)
     ref = F.linear(pooled, w, b)
-    logits = torch.empty(B, NC, device=be.device); probs = torch.empty(B // tta, NC, device=be.device)
+    logits = be.out((B, NC), torch.float32, float("nan")); probs = be.out((B // tta, NC), torch.float32, float("nan"))
     be.call("head_fwd", cabi.make("mds_head_fwd_args", B=B, F=Fdim, NC=NC, pooled=be.t(pooled), mask=None, w=be.t(w), b=be.t(b),
                                   logits=logits, probs=probs, tta=tta))
     be.sync()
@@ -432,15 +432,15 @@ def test_pack_weights(be, dt):
     w3 = torch.randn(20, 12, 3, 3, generator=g); w1 = torch.randn(24, 16, 1, 1, generator=g)
     ws = torch.randn(32, 3, 3, 3, generator=g)
     srcs = [be.t(w3), be.t(w3), be.t(w1), be.t(ws)]
-    dsts = [torch.empty(20 * 9 * 12, dtype=tdt, device=be.device), torch.empty(12 * 9 * 20, dtype=tdt, device=be.device),
-            torch.empty(24 * 16, dtype=tdt, device=be.device), torch.empty(32 * 32, dtype=tdt, device=be.device)]
+    dsts = [be.out(20 * 9 * 12, tdt, float("nan")), be.out(12 * 9 * 20, tdt, float("nan")),
+            be.out(24 * 16, tdt, float("nan")), be.out(32 * 32, tdt, float("nan"))]
     kinds = [(0, 20, 12, 9), (1, 20, 12, 9), (0, 24, 16, 1), (2, 32, 27, 1)]
     Job = cabi.STRUCTS["mds_pack_job"]
     jobs = (Job * 4)()
     for j, (s, d, (k, O, I, t)) in enumerate(zip(srcs, dsts, kinds)):
-        jobs[j].src = s.data_ptr(); jobs[j].dst = d.data_ptr(); jobs[j].kind = k; jobs[j].O = O; jobs[j].I = I; jobs[j].taps = t
-    raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(be.device)
-    be.lib.check(be.lib.fn["pack_weights"](raw.data_ptr(), 4, 20 * 12 * 9, code, be.stream()), "pack_weights")
+        jobs[j].src = be.ptr(s); jobs[j].dst = be.ptr(d); jobs[j].kind = k; jobs[j].O = O; jobs[j].I = I; jobs[j].taps = t
+    raw = be.t(torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8))
+    be.lib.check(be.lib.fn["pack_weights"](be.ptr(raw), 4, 20 * 12 * 9, code, be.stream()), "pack_weights")
     be.sync()
     assert_close(dsts[0].view(20, 9, 12), w3.view(20, 12, 9).permute(0, 2, 1), dt)
     assert_close(dsts[1].view(12, 9, 20), w3.view(20, 12, 9).flip(2).permute(1, 2, 0), dt)
@@ -457,14 +457,14 @@ def test_pack_weights_transposed(be, dt, O, I):
     code, tdt = DT[dt]
     w = torch.randn(O, I, generator=gen(43))
     src = be.t(w)
-    d_flip = torch.empty(I * O, dtype=tdt, device=be.device)
-    d_f32 = torch.empty(I * O, dtype=torch.float32, device=be.device)
+    d_flip = be.out(I * O, tdt, float("nan"))
+    d_f32 = be.out(I * O, torch.float32, float("nan"))
     Job = cabi.STRUCTS["mds_pack_job"]
     jobs = (Job * 2)()
     for j, (d, k) in enumerate(((d_flip, cabi.MDS_PACK_IO_FLIP), (d_f32, cabi.MDS_PACK_IO_F32))):
-        jobs[j].src = src.data_ptr(); jobs[j].dst = d.data_ptr(); jobs[j].kind = k; jobs[j].O = O; jobs[j].I = I; jobs[j].taps = 1
-    raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(be.device)
-    be.lib.check(be.lib.fn["pack_weights"](raw.data_ptr(), 2, O * I, code, be.stream()), "pack_weights")
+        jobs[j].src = be.ptr(src); jobs[j].dst = be.ptr(d); jobs[j].kind = k; jobs[j].O = O; jobs[j].I = I; jobs[j].taps = 1
+    raw = be.t(torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8))
+    be.lib.check(be.lib.fn["pack_weights"](be.ptr(raw), 2, O * I, code, be.stream()), "pack_weights")
     be.sync()
     assert_close(d_flip.view(I, O), w.t(), dt)
     assert torch.equal(d_f32.view(I, O).cpu(), w.t().contiguous())

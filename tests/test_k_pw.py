@@ -55,8 +55,8 @@ def test_pw_fwd(be, dt, M, K, N, mode, res, stats):
     r = torch.randn(M, N, generator=g).to(tdt)
     scale, shift, gate = _mk_pro(be, mode, K, groups, g)
     xd, wd, rd = be.t(x), be.t(w), be.t(r)
-    y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, N, device=be.device, dtype=torch.float64)
+    y = be.out((M, N), tdt, float("nan"))
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, N), torch.float64, 0)
     args = cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=xd, w=wd, y=y,
                      pro=cabi.pro(mode, scale, shift, gate, rpg),
                      residual=rd if res else None, stats=st if stats else None)
@@ -103,7 +103,7 @@ def test_pw_fwd_output_transform(be, dt, M, K, N, pmode, emode, res):
     scale, shift, gate = _mk_pro(be, pmode, K, groups, g)
     esc = 1.0 + 0.3 * torch.randn(N, generator=g); esh = 0.5 * torch.randn(N, generator=g)
     r = torch.randn(M, N, generator=g).to(tdt) if res else None
-    y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
+    y = be.out((M, N), tdt, float("nan"))
     be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                 pro=cabi.pro(pmode, scale, shift, gate, rpg), residual=be.t(r) if res else None, stats=None,
                                 epi=cabi.make("mds_epi_t", mode=emode, scale=be.t(esc), shift=be.t(esh))))
@@ -135,12 +135,12 @@ def test_pw_fwd_split_k(be, dt, M, K, N, pmode, emode, res, split):
     scale, shift, gate = _mk_pro(be, pmode, K, groups, g)
     esc = 1.0 + 0.3 * torch.randn(N, generator=g); esh = 0.5 * torch.randn(N, generator=g)
     r = torch.randn(M, N, generator=g).to(tdt) if res else None
-    part = torch.full((split * M * N,), float("nan"), device=be.device)
+    part = be.out((split * M * N,), torch.float32, float("nan"))
     tiles = -(-M // cabi.MDS_PW_SPLIT_TILE_ROWS) * -(-N // 128)
-    ticket = torch.zeros(tiles * cabi.MDS_PW_SPLIT_TICKET_STRIDE, dtype=torch.int32, device=be.device)
+    ticket = be.out(tiles * cabi.MDS_PW_SPLIT_TICKET_STRIDE, torch.int32, 0)
     outs = []
     for sp in (split, split, 0):
-        y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
+        y = be.out((M, N), tdt, float("nan"))
         epi = cabi.make("mds_epi_t", mode=emode, scale=be.t(esc), shift=be.t(esh)) if emode else cabi.make("mds_epi_t", mode=0)
         be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                     pro=cabi.pro(pmode, scale, shift, gate, rpg), residual=be.t(r) if res else None, stats=None, epi=epi,
@@ -173,10 +173,10 @@ def test_pw_fwd_split_k_handoff_under_load(be_gpu):
     side = torch.cuda.Stream()
     big = torch.empty(64 << 20, dtype=torch.float32, device=dev); big2 = torch.empty_like(big)
     for (M, K, N, S, code, tdt) in [(920, 1152, 192, 12, cabi.MDS_F32, torch.float32), (3680, 672, 112, 4, cabi.MDS_BF16, torch.bfloat16)]:
-        x = torch.randn(M, K, device=dev).to(tdt); w = (torch.randn(N, K, device=dev) / K ** 0.5).to(tdt)
-        y = torch.empty(M, N, device=dev, dtype=tdt)
-        part = torch.empty(S * M * N, device=dev)
-        tk = torch.zeros(-(-M // cabi.MDS_PW_SPLIT_TILE_ROWS) * -(-N // 128) * cabi.MDS_PW_SPLIT_TICKET_STRIDE, dtype=torch.int32, device=dev)
+        x = b.t(torch.randn(M, K, device=dev).to(tdt)); w = b.t((torch.randn(N, K, device=dev) / K ** 0.5).to(tdt))
+        y = b.out((M, N), tdt, float("nan"))
+        part = b.out(S * M * N, torch.float32, float("nan"))
+        tk = b.out(-(-M // cabi.MDS_PW_SPLIT_TILE_ROWS) * -(-N // 128) * cabi.MDS_PW_SPLIT_TICKET_STRIDE, torch.int32, 0)
         a = cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=x, w=w, y=y, pro=cabi.pro(0), residual=None, stats=None,
                       split=S, split_part=part, split_ticket=tk)
         b.call("pw_fwd", a); b.sync()
@@ -189,6 +189,7 @@ def test_pw_fwd_split_k_handoff_under_load(be_gpu):
             part.fill_(float("nan"))
             b.call("pw_fwd", a)
             assert torch.equal(y, ref), it
+        b.sync()
         assert int(tk.abs().sum()) == 0
 
 
@@ -217,7 +218,7 @@ def test_pw_wgrad(be, dt, M, K, N, mode):
     x = torch.randn(M, K, generator=g).to(tdt)
     dy = torch.randn(M, N, generator=g).to(tdt)
     scale, shift, gate = _mk_pro(be, mode, K, groups, g)
-    dw = torch.zeros(N, K, device=be.device)
+    dw = be.out((N, K), torch.float32, 0, name="dw")
     args = cabi.make("mds_pw_wgrad_args", dtype=code, M=M, K=K, N=N, x=be.t(x), dy=be.t(dy), dw=dw,
                      pro=cabi.pro(mode, scale, shift, gate, rpg))
     be.call("pw_wgrad", args)
@@ -234,7 +235,7 @@ def _bn_setup(be, y, gamma, beta, eps=1e-5):
     M, C = y.shape
     st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, C, dtype=torch.float64)
     st[0, 0] = y.float().sum(0); st[0, 1] = (y.float() ** 2).sum(0)
-    out = torch.empty(4, C, device=be.device)
+    out = be.out((4, C), torch.float32, float("nan"))
     be.call("bn_finalize", cabi.make("mds_bn_finalize_args", C=C, count=M, stats=be.t(st), gamma=be.t(gamma), beta=be.t(beta), eps=eps,
                                      momentum=0.1, training=1, running_mean=None, running_var=None, num_batches_tracked=None, out=out))
     return out
@@ -247,7 +248,7 @@ def _bn_bwd_lin(be, g, y, bn, gamma):
     xhat = (y.float() - bnc[2]) * bnc[3]
     st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, C, dtype=torch.float64)          # backward sums: fp64 slots
     st[3, 0] = g.sum(0); st[5, 1] = (g * xhat).sum(0)
-    coef = torch.empty(3, C, device=be.device); lin = torch.empty(3, C, device=be.device)
+    coef = be.out((3, C), torch.float32, float("nan")); lin = be.out((3, C), torch.float32, float("nan"))
     be.call("bn_bwd_finalize", cabi.make("mds_bn_bwd_finalize_args", C=C, count=M, stats=be.t(st), gamma=be.t(gamma), bn=bn, dgamma=None,
                                          dbeta=None, coef=coef, lin=lin, batch_stats=1))
     return lin
@@ -281,16 +282,16 @@ def test_pw_fwd_bn_backward_fusion(be, dt, M, C, N, gmode, res, post):
     z.backward(gsrc_ref)
     dy_ref = yf.grad
     dyd = be.t(dy_ref.to(tdt))
-    out = torch.full((M, N), float("nan")).to(tdt).to(be.device)
+    out = be.out((M, N), tdt, float("nan"))
     # next layer's BatchNorm (the one whose backward sums the epilogue takes)
     ys = (torch.randn(M, N, generator=g_) * 1.2 - 0.2).to(tdt)
     gamma2 = 1 + 0.2 * torch.randn(N, generator=g_); beta2 = 0.1 * torch.randn(N, generator=g_)
     mask2 = (torch.rand(groups, generator=g_) < 0.6).float() / 0.6
     bn2 = _bn_setup(be, ys, gamma2, beta2)
-    st2 = torch.zeros(cabi.MDS_STAT_SLOTS, 2, N, device=be.device, dtype=torch.float64)
+    st2 = be.out((cabi.MDS_STAT_SLOTS, 2, N), torch.float64, 0)
     kw = {}
     if post:
-        kw["post"] = cabi.poststat(post, be.t(ys), bn2, st2, be.t(mask2), rpg)
+        kw["post"] = cabi.poststat(post, be.t(ys), bn2, st2, be.t(mask2, name="mask"), rpg)
     be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=C, N=N, x=dyd, w=be.t(w), y=out, pro=cabi.pro(0),
                                 residual=be.t(r) if res else None, stats=None, **kw))
     be.sync()
@@ -351,8 +352,8 @@ def _run_pw_plain(be, dt, M, K, N, res, stats, post, check_taken, frag=False, fo
     x = torch.randn(M, K, generator=g_).to(tdt)
     w = (torch.randn(N, K, generator=g_) / K ** 0.5).to(tdt)
     r = torch.randn(M, N, generator=g_).to(tdt)
-    out = torch.full((M, N), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, N, device=be.device, dtype=torch.float64)
+    out = be.out((M, N), tdt, float("nan"))
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, N), torch.float64, 0)
     kw = {}
     if post:
         ys = (torch.randn(M, N, generator=g_) * 1.2 - 0.2).to(tdt)
@@ -394,14 +395,14 @@ def _frag_pack(be, w, io=False):
     data-gradient launches do from the [K][N] parameter)"""
     N, K = w.shape
     src = be.t(w.float().t() if io else w.float())
-    dst = torch.empty(-(-K // 32) * -(-N // 16) * 512, dtype=torch.bfloat16, device=be.device)
+    dst = be.out(-(-K // 32) * -(-N // 16) * 512, torch.bfloat16, float("nan"))
     Job = cabi.STRUCTS["mds_pack_job"]
     job = Job()
-    job.src, job.dst = src.data_ptr(), dst.data_ptr()
+    job.src, job.dst = be.ptr(src), be.ptr(dst)
     job.kind = cabi.MDS_PACK_FRAG_IO if io else cabi.MDS_PACK_FRAG_OI
     job.O, job.I, job.taps = (K, N, 1) if io else (N, K, 1)
-    tab = torch.frombuffer(bytearray(bytes(job)), dtype=torch.uint8).to(be.device)
-    be.lib.check(be.lib.fn["pack_weights"](tab.data_ptr(), 1, dst.numel(), cabi.MDS_BF16, be.stream()), "pack_weights")
+    tab = be.t(torch.frombuffer(bytearray(bytes(job)), dtype=torch.uint8))
+    be.lib.check(be.lib.fn["pack_weights"](be.ptr(tab), 1, dst.numel(), cabi.MDS_BF16, be.stream()), "pack_weights")
     be.sync()
     return dst
 
@@ -453,8 +454,8 @@ def _kstream_case(be, M, K, N, mode, stats):
     x = torch.randn(M, K, generator=g).to(tdt)
     w = (torch.randn(N, K, generator=g) / K ** 0.5).to(tdt)
     scale, shift, gate = _mk_pro(be, mode, K, groups, g)
-    y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(cabi.MDS_STAT_SLOTS, 2, N, device=be.device, dtype=torch.float64)
+    y = be.out((M, N), tdt, float("nan"))
+    st = be.out((cabi.MDS_STAT_SLOTS, 2, N), torch.float64, 0)
     be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                 pro=cabi.pro(mode, scale, shift, gate, rpg), residual=None, stats=st if stats else None,
                                 w_frag=_frag_pack(be, w, io=(M % 2 == 1))))

@@ -33,7 +33,7 @@ def _case(N, H, W, Cout, dt, seed):
 
 
 def _launch(be, c, N, H, W, Cout, **kw):
-    dx = torch.full((N, 3, H, W), float("nan"), device=be.device)
+    dx = be.out((N, 3, H, W), torch.float32, float("nan"))
     be.call("stem_dgrad", cabi.make("mds_stem_dgrad_args", dtype=c["code"], N=N, H=H, W=W, OH=c["OH"], OW=c["OW"], Cout=Cout,
                                     pad_t=c["pt"], pad_l=c["pl"], w=be.t(c["w"]), dx=dx, **kw))
     be.sync()
@@ -88,10 +88,10 @@ def test_stem_dgrad_forms_dy_on_load(be, dt, gmode, N, H, W):
 
 def test_stem_dgrad_bad_arguments_are_codes(be):
     c = _case(1, 8, 8, 32, "f32", 3)
-    dx = torch.zeros(1, 3, 8, 8, device=be.device)
+    dx = be.out((1, 3, 8, 8), torch.float32, 0)
     base = dict(dtype=c["code"], N=1, H=8, W=8, OH=c["OH"], OW=c["OW"], Cout=32, pad_t=c["pt"], pad_l=c["pl"], w=be.t(c["w"]),
                 dy=be.t(c["dy"]), dx=dx)
     for bad in (dict(Cout=24), dict(dy=None), dict(dx=None), dict(pad_l=2), dict(N=0)):
         a = cabi.make("mds_stem_dgrad_args", **dict(base, **bad))
-        rc = be.lib.fn["stem_dgrad"](ctypes.byref(a), be.stream())
+        rc = be.rc("stem_dgrad", a)
         assert rc == cabi.MDS_ERR_BAD_ARG and b"stem_dgrad" in be.lib.dll.mds_last_error(), bad

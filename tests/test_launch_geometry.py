@@ -66,7 +66,7 @@ def bn_forward_table(be, y, gamma, beta, eps):
     M, C = y.shape
     stats = torch.zeros(SLOTS, 2, C, dtype=F64)
     stats[0, 0] = y.to(F64).sum(0); stats[0, 1] = (y.to(F64) ** 2).sum(0)
-    out = torch.empty(4, C, device=be.device)
+    out = be.out((4, C), torch.float32, float("nan"))
     be.call("bn_finalize", cabi.make("mds_bn_finalize_args", C=C, count=M, stats=be.t(stats), gamma=be.t(gamma), beta=be.t(beta),
                                      eps=eps, momentum=0.1, training=1, running_mean=None, running_var=None,
                                      num_batches_tracked=None, out=out))
@@ -97,12 +97,12 @@ def test_bn_backward_chain_grid_stride_trips(be, dt, mode, C, M, cap):
     dy_ref, dgamma_ref, dbeta_ref = bn_bwd_reference(y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps)
     bn = bn_forward_table(be, y, gamma, beta, eps)
     gs = cabi.gsrc(mode, be.t(u), be.t(gate), be.t(dpool), be.t(mask), rpg)
-    st2 = torch.zeros(SLOTS, 2, C, device=be.device, dtype=F64)
+    st2 = be.out((SLOTS, 2, C), F64, 0)
     yd = be.t(y)
-    dgamma = torch.zeros(C, device=be.device); dbeta = torch.zeros(C, device=be.device)
-    coef = torch.empty(3, C, device=be.device)
+    dgamma = be.out(C, torch.float32, 0); dbeta = be.out(C, torch.float32, 0)
+    coef = be.out((3, C), torch.float32, float("nan"))
     guard = 2 * 3 * 51 + 14      # rows behind dy that must stay NaN: more than the two row slots of the longest stride reach past M
-    buf = torch.full((M + guard, C), float("nan")).to(tdt).to(be.device)
+    buf = be.out((M + guard, C), tdt, float("nan"))
     dy = buf[:M]
     with knobs(be, {cabi.MDS_KNOB_STREAM_BLOCKS: cap, cabi.MDS_KNOB_REDUCE_BLOCKS: cap}):
         be.call("bn_bwd_reduce", cabi.make("mds_bn_bwd_reduce_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, stats=st2))
@@ -136,7 +136,7 @@ def test_bn_res_grid_stride_trips(be, dt, M, C, cap):
     y = torch.randn(M, C, generator=g).to(tdt); sc_ = torch.randn(M, C, generator=g).to(tdt)
     scale = 1 + 0.2 * torch.randn(C, generator=g); shift = 0.2 * torch.randn(C, generator=g)
     mask = (torch.rand(cdiv(M, rpg), generator=g) > 0.3).float() / 0.7
-    out = torch.full((M, C), float("nan")).to(tdt).to(be.device)
+    out = be.out((M, C), tdt, float("nan"))
     with knobs(be, {cabi.MDS_KNOB_STREAM_BLOCKS: cap}):
         be.call("bn_res", cabi.make("mds_bn_res_args", dtype=code, M=M, C=C, y=be.t(y), scale=be.t(scale), shift=be.t(shift), act=1,
                                     mask=be.t(mask), rows_per_group=rpg, shortcut=be.t(sc_), out=out))
@@ -180,18 +180,18 @@ def test_se_grouped_reduces_several_blocks_per_group(be, dt, C, RD):
     # kernels
     yd, ud, scd, shd = be.t(y), be.t(u), be.t(scale), be.t(shift)
     w1d, b1d, w2d, b2d = be.t(w1), be.t(b1), be.t(w2), be.t(b2)
-    pooled = torch.zeros(G, C, device=be.device, dtype=F64); pooled_m = torch.zeros_like(pooled)
-    act = torch.full((M, C), float("nan")).to(tdt).to(be.device)
-    hidden = torch.empty(G, RD, device=be.device); gate = torch.empty(G, C, device=be.device)
-    dgate = torch.zeros(G, C, device=be.device, dtype=F64); dgate_m = torch.zeros_like(dgate)
-    dpooled = torch.empty(G, C, device=be.device)
-    dw1 = torch.zeros(RD, C, device=be.device); db1 = torch.zeros(RD, device=be.device)
-    dw2 = torch.zeros(C, RD, device=be.device); db2 = torch.zeros(C, device=be.device)
-    bn_stats = torch.zeros(SLOTS, 2, C, device=be.device, dtype=F64)
+    pooled = be.out((G, C), F64, 0); pooled_m = be.out((G, C), F64, 0)
+    act = be.out((M, C), tdt, float("nan"))
+    hidden = be.out((G, RD), torch.float32, float("nan")); gate = be.out((G, C), torch.float32, float("nan"))
+    dgate = be.out((G, C), F64, 0); dgate_m = be.out((G, C), F64, 0)
+    dpooled = be.out((G, C), torch.float32, float("nan"))
+    dw1 = be.out((RD, C), torch.float32, 0); db1 = be.out(RD, torch.float32, 0)
+    dw2 = be.out((C, RD), torch.float32, 0); db2 = be.out(C, torch.float32, 0)
+    bn_stats = be.out((SLOTS, 2, C), F64, 0)
     with knobs(be, {cabi.MDS_KNOB_REDUCE_PASSES: 1}):
         nblk = be.lib.fn["se_bwd_reduce_blocks"](R_, C)
         assert nblk >= 2
-        bnsums = torch.full((G, nblk, 4, C), float("nan"), device=be.device)
+        bnsums = be.out((G, nblk, 4, C), torch.float32, float("nan"))
         be.call("se_pool", cabi.make("mds_se_pool_args", dtype=code, groups=G, rows_per_group=R_, C=C, y=yd, scale=scd, shift=shd,
                                      pooled=pooled, act=act))
         be.call("se_pool", cabi.make("mds_se_pool_args", dtype=code, groups=G, rows_per_group=R_, C=C, y=act, scale=None, shift=None,
@@ -204,7 +204,7 @@ def test_se_grouped_reduces_several_blocks_per_group(be, dt, C, RD):
                                            scale=None, shift=None, dgate=dgate_m))
         be.call("se_fc_bwd", cabi.make("mds_se_fc_bwd_args", groups=G, C=C, R=RD, rows_per_group=R_, dgate=dgate, gate=gate,
                                        hidden=hidden, pooled=pooled, w1=w1d, w2=w2d, dpooled=dpooled,
-                                       scratch=torch.empty(G, RD, device=be.device), dw1=dw1, db1=db1, dw2=dw2, db2=db2,
+                                       scratch=be.out((G, RD), torch.float32, float("nan")), dw1=dw1, db1=db1, dw2=dw2, db2=db2,
                                        bnsums=bnsums, bn_nblk=nblk, bn_stats=bn_stats))
         be.sync()
         for name in ("se_pool_kernel", "se_bwd_reduce_kernel"):
@@ -294,8 +294,8 @@ def test_pw_fwd_large_tiles(be, dt, M, N, gy, pmode, res, stats):
     code, tdt = DT[dt]
     K, rpg = PW_K, 50
     g, x, w, r, scale, shift, gate = pw_operands(be, dt, M, K, N, pmode, rpg, M * 7 + N + pmode)
-    y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
-    st = torch.zeros(SLOTS, 2, N, device=be.device, dtype=F64)
+    y = be.out((M, N), tdt, float("nan"))
+    st = be.out((SLOTS, 2, N), F64, 0)
     with knobs(be, pw_knobs(gy)):
         be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                     pro=cabi.pro(pmode, be.t(scale), be.t(shift), be.t(gate), rpg),
@@ -336,8 +336,8 @@ def test_pw_fwd_large_tiles_data_gradient(be, dt, M, N, gy, gmode, res, post):
     gamma2 = 1 + 0.2 * torch.randn(N, generator=g_); beta2 = 0.1 * torch.randn(N, generator=g_)
     mask2 = (torch.rand(groups, generator=g_) < 0.6).float() / 0.6
     bn2 = bn_forward_table(be, ys, gamma2, beta2, 1e-5)
-    st2 = torch.zeros(SLOTS, 2, N, device=be.device, dtype=F64)
-    out = torch.full((M, N), float("nan")).to(tdt).to(be.device)
+    st2 = be.out((SLOTS, 2, N), F64, 0)
+    out = be.out((M, N), tdt, float("nan"))
     with knobs(be, pw_knobs(gy)):
         be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=C, N=N, x=be.t(dy), w=be.t(w), y=out, pro=cabi.pro(0),
                                     residual=be.t(r) if res else None, stats=None,
@@ -374,7 +374,7 @@ def test_pw_fwd_large_tiles_output_transform(be, dt, M, N, gy, pmode, emode, res
     K, rpg = PW_K, 97
     g, x, w, r, scale, shift, gate = pw_operands(be, dt, M, K, N, pmode, rpg, M + N + emode)
     esc = 1.0 + 0.3 * torch.randn(N, generator=g); esh = 0.5 * torch.randn(N, generator=g)
-    y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
+    y = be.out((M, N), tdt, float("nan"))
     with knobs(be, pw_knobs(gy)):
         be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                     pro=cabi.pro(pmode, be.t(scale), be.t(shift), be.t(gate), rpg), residual=be.t(r) if res else None,
@@ -397,7 +397,7 @@ def test_pw_fwd_one_or_two_chunks_in_flight(be, pmode):
     ref = pw_epi_reference(x, w, None, pmode, scale, shift, gate, rpg, esc, esh, emode, tdt)
     names = []
     for deep_off in (0, 1):
-        y = torch.full((M, N), float("nan"), device=be.device)
+        y = be.out((M, N), torch.float32, float("nan"))
         with knobs(be, {cabi.MDS_KNOB_PW_DEEP: deep_off}):
             be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                         pro=cabi.pro(pmode, be.t(scale), be.t(shift), be.t(gate), rpg), residual=None, stats=None,
@@ -430,12 +430,12 @@ def test_pw_fwd_split_rule_with_a_forced_factor(be, dt, knob):
         assert f(M, 18 * kc, N, code) == min(knob, 6)                                # chunks / 3 caps the factor
         g, x, w, r, scale, shift, gate = pw_operands(be, dt, M, K, N, pmode, rpg, 23 + knob)
         esc = 1.0 + 0.3 * torch.randn(N, generator=g); esh = 0.5 * torch.randn(N, generator=g)
-        part = torch.full((split * M * N,), float("nan"), device=be.device)
+        part = be.out((split * M * N,), torch.float32, float("nan"))
         tiles = cdiv(M, cabi.MDS_PW_SPLIT_TILE_ROWS) * cdiv(N, 128)
-        ticket = torch.zeros(tiles * cabi.MDS_PW_SPLIT_TICKET_STRIDE, dtype=torch.int32, device=be.device)
+        ticket = be.out(tiles * cabi.MDS_PW_SPLIT_TICKET_STRIDE, torch.int32, 0)
         outs = []
         for _ in range(2):
-            y = torch.full((M, N), float("nan")).to(tdt).to(be.device)
+            y = be.out((M, N), tdt, float("nan"))
             be.call("pw_fwd", cabi.make("mds_pw_fwd_args", dtype=code, M=M, K=K, N=N, x=be.t(x), w=be.t(w), y=y,
                                         pro=cabi.pro(pmode, be.t(scale), be.t(shift), be.t(gate), rpg), residual=be.t(r), stats=None,
                                         epi=cabi.make("mds_epi_t", mode=emode, scale=be.t(esc), shift=be.t(esh)),
@@ -471,14 +471,14 @@ def test_pw_wgrad_block_budget(be, dt, budget, M, det):
     outs = []
     with knobs(be, {cabi.MDS_KNOB_WG_BLOCKS: budget}):
         for run in range(2 if det else 1):
-            dw = torch.zeros(N, K, device=be.device)
+            dw = be.out((N, K), torch.float32, 0)
             args = cabi.make("mds_pw_wgrad_args", dtype=code, M=M, K=K, N=N, x=be.t(x), dy=be.t(dy), dw=dw,
                              pro=cabi.pro(pmode, be.t(scale), be.t(shift), be.t(gate), rpg))
             need = int(be.lib.fn["pw_wgrad_partial_floats"](ctypes.byref(args)))
             assert need > 0 and need % (N * K) == 0
             splits = need // (N * K)
             if det:
-                part = torch.full((need,), float("nan"), device=be.device)
+                part = be.out((need,), torch.float32, float("nan"))
                 args.partial = cabi.make("mds_partial_t", buf=part, floats=need - 1)
                 with pytest.raises(cabi.MdsError):
                     be.call("pw_wgrad", args)
