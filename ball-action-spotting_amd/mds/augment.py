@@ -15,6 +15,9 @@ Drop-in for ``get_train_augmentations(size)`` of ``src/ball_action/augmentations
   the samples that drew them (p = 0.2 each) take one extra pass each through a scratch buffer, the others do not.
 
 No CPU fallback: CPU tensors raise unless the test-suite's kernel simulator has been injected (``TrainAugmentations._lib``).
+
+``TimmMixup`` (below the augmentations) is the drop-in for ``src/mixup.py::TimmMixup``: mixup / cutmix of the batch in one
+in-place launch (``mds_mixup``).
 """
 from __future__ import annotations
 
@@ -309,6 +312,166 @@ class _Null:
 
     def __exit__(self, *a):
         return False
+
+
+# ------------------------------------------------------------------------------------------------ mixup / cutmix
+class TimmMixup:
+    """Drop-in for ``src/mixup.py::TimmMixup`` (timm 0.9.2's ``Mixup`` with sample i paired with sample B - 1 - i; installed
+    from ``config["mixup_params"]``, called at ``src/argus_models.py:52-53``): the same constructor, the same attribute names,
+    the same ``np.random`` draws in the same order - and ONE in-place launch (``mds_mixup``) where the reference clones or
+    flips the batch and passes over it three to five times.  The per-sample jobs travel in the kernel arguments.
+
+    ``__call__(x, target)``: x is the (B, T, H, W) float32 contiguous batch on the device, mixed IN PLACE and returned;
+    target is (B, ...), left untouched - the smoothed, mixed target comes back as a new float32 tensor of its shape.
+    ``rng``: a ``np.random.RandomState`` to draw from; None = the global ``np.random`` (as timm does).
+    No eager fallback: CPU tensors raise unless the test-suite's kernel simulator has been injected (``_lib``)."""
+
+    def __init__(self, mixup_alpha=1., cutmix_alpha=0., cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode='batch',
+                 correct_lam=True, label_smoothing=0.1, num_classes=1000, *, rng=None):
+        self.mixup_alpha = mixup_alpha
+        self.cutmix_alpha = cutmix_alpha
+        self.cutmix_minmax = cutmix_minmax
+        if self.cutmix_minmax is not None:
+            assert len(self.cutmix_minmax) == 2
+            self.cutmix_alpha = 1.0          # the box is drawn from the min / max ratios, lam follows from it
+        self.mix_prob = prob
+        self.switch_prob = switch_prob
+        self.label_smoothing = label_smoothing
+        self.num_classes = num_classes
+        self.mode = mode
+        self.correct_lam = correct_lam
+        self.mixup_enabled = True
+        self.rng = rng
+        self._lib = None          # tests inject the kernel simulator here
+        self._last = None
+
+    # ------------------------------------------------------------------ the reference's draws
+    @property
+    def _np(self):
+        return np.random if self.rng is None else self.rng
+
+    def _params_per_elem(self, batch_size):
+        rnd = self._np
+        lam = np.ones(batch_size, dtype=np.float32)
+        use_cutmix = np.zeros(batch_size, dtype=bool)
+        if self.mixup_enabled:
+            if self.mixup_alpha > 0. and self.cutmix_alpha > 0.:
+                use_cutmix = rnd.rand(batch_size) < self.switch_prob
+                lam_cut = rnd.beta(self.cutmix_alpha, self.cutmix_alpha, size=batch_size)       # both vectors are always drawn
+                lam_mix = np.where(use_cutmix, lam_cut, rnd.beta(self.mixup_alpha, self.mixup_alpha, size=batch_size))
+            elif self.mixup_alpha > 0.:
+                lam_mix = rnd.beta(self.mixup_alpha, self.mixup_alpha, size=batch_size)
+            elif self.cutmix_alpha > 0.:
+                use_cutmix = np.ones(batch_size, dtype=bool)
+                lam_mix = rnd.beta(self.cutmix_alpha, self.cutmix_alpha, size=batch_size)
+            else:
+                assert False, "One of mixup_alpha > 0., cutmix_alpha > 0., cutmix_minmax not None should be true."
+            lam = np.where(rnd.rand(batch_size) < self.mix_prob, lam_mix.astype(np.float32), lam)
+        return lam, use_cutmix
+
+    def _params_per_batch(self):
+        rnd = self._np
+        lam, use_cutmix = 1., False
+        if self.mixup_enabled and rnd.rand() < self.mix_prob:
+            if self.mixup_alpha > 0. and self.cutmix_alpha > 0.:
+                use_cutmix = rnd.rand() < self.switch_prob
+                lam_mix = rnd.beta(self.cutmix_alpha, self.cutmix_alpha) if use_cutmix else rnd.beta(self.mixup_alpha, self.mixup_alpha)
+            elif self.mixup_alpha > 0.:
+                lam_mix = rnd.beta(self.mixup_alpha, self.mixup_alpha)
+            elif self.cutmix_alpha > 0.:
+                use_cutmix = True
+                lam_mix = rnd.beta(self.cutmix_alpha, self.cutmix_alpha)
+            else:
+                assert False, "One of mixup_alpha > 0., cutmix_alpha > 0., cutmix_minmax not None should be true."
+            lam = float(lam_mix)
+        return lam, use_cutmix
+
+    def _bbox_and_lam(self, h, w, lam):
+        """timm's cutmix_bbox_and_lam over (h, w): ((yl, yh, xl, xh), lam); `lam` keeps the type it arrives in (a Python float
+        in batch mode, an np.float32 in elem / pair mode) - the box edges depend on it"""
+        rnd = self._np
+        if self.cutmix_minmax is not None:
+            lo, hi = self.cutmix_minmax
+            cut_h = rnd.randint(int(h * lo), int(h * hi))
+            cut_w = rnd.randint(int(w * lo), int(w * hi))
+            yl = rnd.randint(0, h - cut_h)
+            xl = rnd.randint(0, w - cut_w)
+            yh, xh = yl + cut_h, xl + cut_w
+        else:
+            ratio = np.sqrt(1 - lam)
+            cut_h, cut_w = int(h * ratio), int(w * ratio)
+            cy = rnd.randint(0, h)
+            cx = rnd.randint(0, w)
+            yl, yh = np.clip(cy - cut_h // 2, 0, h), np.clip(cy + cut_h // 2, 0, h)
+            xl, xh = np.clip(cx - cut_w // 2, 0, w), np.clip(cx + cut_w // 2, 0, w)
+        if self.correct_lam or self.cutmix_minmax is not None:
+            lam = 1. - ((yh - yl) * (xh - xl)) / float(h * w)
+        return (int(yl), int(yh), int(xl), int(xh)), lam
+
+    def _jobs(self, b, h, w):
+        """per sample (mode, lam32, oml32, box) in the reference's draw order; plus whether any image job does something"""
+        none = (cabi.MDS_MIX_NONE, np.float32(1), np.float32(0), (0, 0, 0, 0))
+        if self.mode == 'batch':
+            lam, use_cutmix = self._params_per_batch()
+            if lam == 1.:
+                return [none] * b
+            if use_cutmix:
+                box, lam = self._bbox_and_lam(h, w, lam)
+                return [(cabi.MDS_MIX_CUT, np.float32(lam), np.float32(1. - lam), box)] * b
+            return [(cabi.MDS_MIX_BLEND, np.float32(lam), np.float32(1. - lam), (0, 0, 0, 0))] * b       # 1 - lam in double, then rounded
+        n = b if self.mode == 'elem' else b // 2
+        lam_batch, use_cutmix = self._params_per_elem(n)
+        mode, boxes = [cabi.MDS_MIX_NONE] * n, [(0, 0, 0, 0)] * n
+        for i in range(n):
+            lam = lam_batch[i]
+            if lam != 1.:
+                if use_cutmix[i]:
+                    boxes[i], lam = self._bbox_and_lam(h, w, lam)
+                    lam_batch[i] = lam               # the corrected lam, rounded to fp32 by the vector
+                    mode[i] = cabi.MDS_MIX_CUT
+                else:
+                    mode[i] = cabi.MDS_MIX_BLEND
+        jobs = [(mode[i], lam_batch[i], np.float32(1) - lam_batch[i], boxes[i]) for i in range(n)]       # 1 - lam in fp32
+        return jobs if self.mode == 'elem' else jobs + jobs[::-1]
+
+    # ------------------------------------------------------------------ launch
+    def _library(self, x):
+        if self._lib is not None:
+            return self._lib
+        if not x.is_cuda:
+            raise cabi.MdsError("mds.augment.TimmMixup runs on MI355X only: move the batch to cuda")
+        return cabi.load()
+
+    @torch.no_grad()
+    def __call__(self, x, target):
+        assert len(x) % 2 == 0, 'Batch size should be even when using this'
+        if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()):
+            raise cabi.MdsError("TimmMixup mixes the (B, T, H, W) float32 contiguous frame batch in place: a copy would not reach the caller's tensor")
+        if self.mode not in ('batch', 'elem', 'pair'):
+            raise cabi.MdsError(f"TimmMixup: mode '{self.mode}' (batch, elem or pair)")
+        lib = self._library(x)
+        b, t, h, w = x.shape
+        if target.device != x.device or target.shape[0] != b:
+            raise cabi.MdsError("TimmMixup: target is (B, ...) on the batch's device")
+        tgt = target.reshape(b, -1).to(torch.float32).contiguous()
+        out = torch.empty_like(tgt)
+        assert out.data_ptr() != tgt.data_ptr()
+        jobs = self._jobs(b, h, w)
+        off_value = self.label_smoothing / self.num_classes
+        on_value = 1. - self.label_smoothing + off_value
+        stream = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else 0
+        with torch.cuda.device(x.device) if x.is_cuda else _Null():
+            for p0 in range(0, b // 2, cabi.MDS_MIX_MAX_PAIRS):
+                npairs = min(cabi.MDS_MIX_MAX_PAIRS, b // 2 - p0)
+                args = cabi.make("mds_mixup_args", B=b, T=t, H=h, W=w, x=x, pair0=p0, npairs=npairs, target=tgt, target_out=out,
+                                 C=tgt.shape[1], off_value=off_value, on_value=on_value)
+                for k in range(npairs):
+                    for slot, s in ((args.lo[k], p0 + k), (args.hi[k], b - 1 - (p0 + k))):
+                        slot.mode, slot.lam, slot.oml = jobs[s][0], float(jobs[s][1]), float(jobs[s][2])
+                        slot.yl, slot.yh, slot.xl, slot.xh = jobs[s][3]
+                lib.check(lib.fn["mixup"](C.byref(args), stream), "mixup")
+        self._last = (x, tgt, out)      # the launches are asynchronous: their operands outlive this call
+        return x, out.view(target.shape)
 
 
 def get_train_augmentations(size, compose_geometric: bool = False) -> nn.Module:

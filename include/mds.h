@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 138
+#define MDS_VERSION 139
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -888,6 +888,50 @@ typedef struct {
   const float* noise;         /* optional device (B, T, H, W) standard-normal draws; NULL = generate */
 } mds_aug_args;
 int mds_aug_pass(const mds_aug_args* a, mds_stream_t stream);
+
+/* ---- Mixup / CutMix of the frame batch, in place (reference src/mixup.py::TimmMixup = timm's Mixup with the batch paired
+ * front to back, call site src/argus_models.py:52-53).  Sample i is combined with sample j = B - 1 - i.  One launch covers
+ * pairs p = pair0 .. pair0 + npairs - 1 (i = p, j = B - 1 - p), all T planes: the two samples of a pair are read once, both
+ * results are formed from the two ORIGINAL values, and each is written once - no copy of the batch exists.  Every sample has a
+ * job:
+ *   NONE   the sample is not written; a pair of two NONE jobs is neither read nor written
+ *   BLEND  out = fl(fl(a * lam) + fl(b * oml))          a = the sample's own value, b = its partner's
+ *   CUT    out = b inside rows [yl, yh) x columns [xl, xh) of every plane; outside the box nothing is read or written.
+ *          An empty box (yl == yh or xl == xh) does nothing.
+ * Arithmetic (normative): fl() is ONE IEEE fp32 rounding to nearest even; every product and every sum is rounded on its own,
+ * nothing is contracted into a fused multiply-add.  With lam / oml formed as the reference forms them, the launch equals the
+ * reference's torch expressions bit for bit.
+ * Targets (optional, same launch): for every row r of this launch's pairs and c < C
+ *   y1[r][c]  = fl(fl(fl(1 - target[r][c]) * off_value) + fl(target[r][c] * on_value))
+ *   target_out[r][c] = fl(fl(y1[r][c] * lam_r) + fl(y1[B - 1 - r][c] * oml_r))
+ * with lam_r / oml_r of sample r's job whatever its mode (the caller sets lam = 1, oml = 0 for NONE and the box-corrected
+ * lam for CUT).  `target` is only read; `target_out` is another buffer, of which only the rows of this launch's pairs are written.
+ * x, target and target_out need 4-byte alignment only (16-byte vectors are used where x is 16-byte aligned, W % 4 == 0 and a
+ * row segment is covered in full).  The jobs travel in the kernel arguments: a step needs no host-to-device copy.
+ * Refused with MDS_ERR_BAD_ARG: B odd or < 2, npairs outside 1 .. MDS_MIX_MAX_PAIRS, pair0 < 0 or pair0 + npairs > B / 2,
+ * a mode outside 0 .. 2, a box outside [0, H] x [0, W] or with yl > yh / xl > xh, x == NULL, target without target_out or
+ * with C < 1, target_out overlapping target.  Returns 0, or a negative MDS_ERR_* code.                                     */
+#define MDS_MIX_NONE 0
+#define MDS_MIX_BLEND 1
+#define MDS_MIX_CUT 2
+#define MDS_MIX_MAX_PAIRS 32
+typedef struct {
+  int mode;                   /* MDS_MIX_* */
+  float lam, oml;             /* BLEND: the two weights; every mode: the weights of the sample's target row */
+  int yl, yh, xl, xh;         /* CUT: the box */
+} mds_mix_job;
+typedef struct {
+  int B, T, H, W;             /* x: (B, T, H, W) fp32, contiguous, modified IN PLACE; T * H * W < 2^31 */
+  float* x;
+  int pair0, npairs;
+  mds_mix_job lo[MDS_MIX_MAX_PAIRS];   /* job of sample i = pair0 + k           */
+  mds_mix_job hi[MDS_MIX_MAX_PAIRS];   /* job of sample j = B - 1 - (pair0 + k) */
+  const float* target;        /* optional (B, C) fp32; NULL: images only */
+  float* target_out;          /* (B, C) fp32 */
+  int C;
+  float off_value, on_value;
+} mds_mixup_args;
+long mds_mixup(const mds_mixup_args* a, mds_stream_t stream);
 
 /* ---- SURVEY 8(f) N1 (predictor glue): row gather / scatter between the predictor's device rings and the plans' buffers -
  * raw frames ring -> the stem's uint8 input, 2D features -> the feature store, the store's five stacks -> the tail's
