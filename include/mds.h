@@ -26,6 +26,21 @@
  *    (`pooled`), its backward (`dgate`) and the row-split GeM accumulators: all fp64.  What is left to fp32 atomics
  *    are the parameter-gradient accumulations (weight-gradient arena, GeM's dp), which feed nothing else in the step -
  *    and those have a second, fixed-order way out (mds_partial_t below) for runs that must repeat bit for bit.
+ *    WHICH values are summed (tests/backends.py assert_sum_close holds every one of these sums to the fp32 summation bound
+ *    against float64 on exactly these operands):
+ *      - `stats` of mds_pw_fwd / mds_conv_fwd / mds_stem_fwd / mds_dw_fwd: the fp32 ACCUMULATORS (+ the residual where one is
+ *        added), before the store rounds them to the storage type - not the stored y.  Their operands are the stored x (and
+ *        packed w) through the prologue; the bf16 GEMM / convolution kernels round the activated operand to bf16 once
+ *        (after the gate, where there is one).  The depthwise kernels keep the activation in fp32 registers, un-rounded -
+ *        except the LDS-tiled bf16 forward (dw_fwd_kernel, reached by bf16 launches only under MDS_KNOB_DW3G = 1), whose
+ *        tile holds it in the storage type.
+ *      - `post.stats` (mds_poststat_t): the STORED values - g = the bf16 / fp32 number written to y (x the DropPath factor),
+ *        what every later reader of u will read - and xhat = (post.y - mean) * rstd from the fp32 table.
+ *      - `stats` of mds_dw_bwd: the fp32 register value gv = (sum dy * w) * silu'(z), before g is stored; xhat from the
+ *        stored x and the fp32 mean / rstd.  `stats` of mds_bn_bwd_reduce: g formed in fp32 from the stored u (mds_gsrc_t).
+ *      - `dw` of mds_pw_wgrad / mds_conv_wgrad / mds_stem_wgrad: stored dy (or, with a dy prologue, the fp32 dy formed on
+ *        load, un-rounded) times the operand as the forward kernel of the same type holds it (bf16: rounded once).
+ *        `dw` of mds_dw_bwd: stored dy times the fp32 un-rounded activation.
  *  - Alignment.  16 bytes: activations, residuals, filters and packed weights, the per-channel fp32 tables (scale / shift /
  *    bn / coef / lin / gate / dpooled) and the fp64 buffers (stats, pooled, dgate, accum) - the kernels move them in 16-byte
  *    vectors.  4 bytes: the fp32 buffers a planner carves densely out of arenas, which the kernels reach by scalar loads,

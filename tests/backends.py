@@ -12,6 +12,10 @@ the least-aligned pointer the engine's dense arenas (Lazy.sub, carve, Plan.grad)
 with its pattern bit for bit and raises AssertionError naming buffer, side and byte offset; Backend.call() refuses a tensor that
 is not a guarded buffer; the fixtures verify once more on teardown and fail a test that left a launch unverified.
 
+Two assertions: assert_close for elementwise outputs (the error is the store's rounding), assert_sum_close for every output that is
+a sum over rows, pixels or groups - float64 on the operands the kernel holds, the a-priori fp32 summation bound on magnitudes, and
+probes (wrong sums built from the reference) that the bound must still resolve.  tests/test_sum_bounds.py holds the helpers to that.
+
 Out of scope, because they allocate inside product code (Plan / engine arenas, torch modules): test_train_ops.py,
 test_augment.py, and the module, predictor and parallel tests - they use Backend only for its library handle and t()."""
 import contextlib
@@ -279,6 +283,11 @@ def tol(dt):
 
 
 def assert_close(got, want, dt, scale=1.0, msg=""):
+    """elementwise outputs (y, dx, g, out, dy, da): their error is the store's rounding.  A sum over rows, pixels or groups is NOT
+    checked here: a tolerance that grows with the size of the sum (scale = sqrt(count), 20, 10 ...) on top of max|want|, which
+    grows with it too, lets a bf16 sum with a whole image missing pass - such quantities go to assert_sum_close."""
+    assert scale <= 4, (f"{msg}: assert_close(scale={scale:.3g}) - a size-scaled tolerance is refused; a quantity that is a sum is "
+                        f"checked by assert_sum_close (float64 reference of the same operands + the fp32 summation bound)")
     got = got.detach().float().cpu()
     want = want.detach().float().cpu()
     t = tol(dt)
@@ -287,3 +296,130 @@ def assert_close(got, want, dt, scale=1.0, msg=""):
     bad = ~(err <= bound)       # (not `err > bound`: a NaN result - a consumed over-read of a NaN guard - compares False both ways)
     assert not bad.any(), (f"{msg}: {int(bad.sum())}/{bad.numel()} mismatches, max err {err.max().item():.3e} "
                            f"(ref max {want.abs().max().item():.3e}) first bad idx {bad.nonzero()[0].tolist()}")
+
+
+# ------------------------------------------------------------------------------------------------ sums: a derived bound
+U = 2.0 ** -23        # one fp32 ulp (twice the unit roundoff: the bound also holds for adders that truncate)
+SUM_OBSERVERS = []    # callables (msg, worst err / bound) a measuring run may register (profiles/LOG.md's table); empty in the suite
+ABS = 1.0 / U         # `chain` of a part whose `mag` already IS an absolute error bound: (ABS + 8) * U * mag = mag (1 + 1e-6)
+
+
+def assert_sum_close(got, want, parts, msg, probes=(), cap=None):
+    """a kernel output that is an fp32 (then fp64) SUM of values the kernel holds exactly, against `want`: the float64 evaluation of
+    the same sum over the same operands (inputs rounded to the storage type, activations rounded where the kernel rounds them).
+
+    parts: [(chain, mag), ...] - mag: float64, shaped like want, the same computation on absolute values; chain: the number of fp32
+    additions on the longest path into one output element.  bound = U * sum_i (chain_i + 8) * mag_i, U = 2^-23: the a-priori bound
+    of a sum of chain_i terms taken in ANY order ((n - 1) u sum|t| to first order, u = 2^-24), with u doubled so that it holds for
+    a matrix unit whose adders truncate; + 8 for the few fp32 roundings inside one term (a product, (y - mu) * rstd, a mask
+    factor).  Neither figure is fitted to results.  A part (ABS, mag) adds mag itself: the error of operands the kernel computes
+    (pro_operand below).
+
+    cap = (dt, scale): the bound that assert_close(dt, scale) applied to this quantity before; the smaller of the two holds for
+    every element, so nothing is checked more loosely than it was.
+
+    probes: [(name, wrong answer built from the reference alone), ...] - the bound must still tell each of them from `want`: out
+    of bound in at least half of the elements the probe changes.  A probe that changes nothing fails.  NaN in `got` fails."""
+    got = got.detach().double().cpu()
+    want = want.detach().double().cpu()
+    assert got.shape == want.shape, f"{msg}: shape {tuple(got.shape)} vs {tuple(want.shape)}"
+    bound = torch.zeros_like(want)
+    for chain, mag in parts:
+        mag = mag.detach().double().cpu()
+        assert mag.shape == want.shape and bool((mag >= 0).all()), f"{msg}: a part's magnitude is shaped like the result and non-negative"
+        bound = bound + (chain + 8.0) * U * mag
+    if cap is not None:
+        t = tol(cap[0])
+        bound = torch.minimum(bound, t["atol"] * cap[1] * max(1.0, want.abs().max().item()) + t["rtol"] * want.abs())
+    for name, wrong in probes:
+        wrong = wrong.detach().double().cpu()
+        changed = wrong != want
+        assert changed.any(), f"{msg}: probe '{name}' equals the reference: it probes nothing"
+        seen = ((wrong - want).abs() > bound) & changed
+        assert 2 * int(seen.sum()) >= int(changed.sum()), (f"{msg}: the bound does not resolve probe '{name}': out of bound in "
+                                                          f"{int(seen.sum())} of the {int(changed.sum())} elements it changes")
+    err = (got - want).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300)).nan_to_num(nan=float("inf"))
+    for seen_by in SUM_OBSERVERS:
+        seen_by(msg, float(ratio.max()) if ratio.numel() else 0.0)
+    bad = ~(err <= bound)       # (a NaN result compares False both ways)
+    assert not bad.any(), (f"{msg}: {int(bad.sum())}/{bad.numel()} sums out of bound, worst err / bound {ratio.max().item():.3e}, max err "
+                           f"{err.max().item():.3e} (ref max {want.abs().max().item():.3e}) first bad idx {bad.nonzero()[0].tolist()}")
+
+
+def bf16_ulp(a):
+    """distance between the two bf16 numbers around a (float64): 2^(floor(log2|a|) - 7); 0 at 0"""
+    _, e = torch.frexp(a.abs())                     # |a| = m * 2^e, m in [0.5, 1)
+    return torch.where(a == 0, torch.zeros_like(a), torch.ldexp(torch.ones_like(a), e - 8))
+
+
+def near_tie(a, delta):
+    """elements of float64 `a` within relative distance `delta` (a tensor or a number) of a boundary between two bf16 roundings (the
+    midpoint of two neighbouring bf16 numbers): a kernel whose fp32 evaluation of a is off by delta may round it the other way"""
+    m, _ = torch.frexp(a.abs())
+    t = m * 256.0                                   # in [128, 256): the integers are the bf16 numbers, the ties sit at k + 1/2
+    return ((t - torch.floor(t) - 0.5).abs() <= delta * t) & (a != 0)
+
+
+def pro_operand(z, zmag, silu, dt, roundings=0, factor=None):
+    """the operand a kernel FORMS from a stored x: a = act(z) (* factor), z = x * scale + shift, as float64 reference and error bound.
+    z: float64; zmag = |x * scale| + |shift|; silu: False = affine only; factor: the squeeze-excite gate (one more product).
+    Returns (a, err): for bf16, a is rounded to bf16 (round to nearest even, as the kernels' conversion) and err is one bf16 ulp on
+    the NEAR-TIE elements - those within relative distance delta of a rounding boundary, where the kernel's fp32 value may fall on
+    the other side - and 0 elsewhere; for f32, a is not rounded and err = delta * |a|.  delta, per element, from the kernel's
+    arithmetic (csrc/platform.h: silu(z) = z * rcp(1 + exp2(-z * log2(e)))) and the accuracy the CDNA ISA guide documents for
+    v_exp_f32 and v_rcp_f32, 1 ulp each:
+      z itself: two fp32 roundings (or one fused), |dz| <= U * zmag, which moves silu(z) by |dz * silu'(z)|;
+      the exponent's argument: product and constant rounded, relative U, i.e. |z| U on exp2's result; exp2: U; 1 + e: U / 2;
+      rcp: U; the product with z: U / 2; `roundings` more for later factors: (|z| + 4 + roundings) U in all.
+    (An issue-style part (2^-8 / U, mag on the ties) would take 2^-8 |a| for the flip; the exact ulp is between 1 and 2 times that.)"""
+    if silu:
+        s = torch.sigmoid(z)
+        a = z * s
+        da = U * zmag * (s * (1 + z * (1 - s))).abs() + (z.abs() + 4 + roundings) * U * a.abs()
+    else:
+        a = z
+        da = U * zmag + roundings * U * a.abs()
+    if factor is not None:
+        a, da = a * factor, da * factor.abs() + U * (a * factor).abs()
+    if dt != "bf16":
+        return a, da
+    tie = near_tie(a, da / a.abs().clamp_min(1e-300))
+    aq = a.to(torch.bfloat16).double()
+    return aq, torch.where(tie, bf16_ulp(a), torch.zeros_like(a))
+
+
+def stat_parts(v, vabs, K, cnt, verr=None):
+    """forward statistics of a GEMM / convolution with inner length K over cnt pixels, reduced over every dimension but the last.
+    v: float64 values the kernel sums (its fp32 accumulators, + residual where the kernel adds one first), vabs: the same product on
+    absolute values, verr: the product of the operand's error (pro_operand) with |w|.  Returns {"sum": (want, parts), "sumsq": ...}"""
+    red = tuple(range(v.dim() - 1))
+    sq = (v * v).sum(red)
+    ps = [(K, vabs.sum(red)), (cnt, v.abs().sum(red))]
+    pq = [(2 * K + 2, (vabs * vabs).sum(red)), (cnt, sq)]
+    if verr is not None:
+        ps.append((ABS, verr.sum(red)))
+        pq.append((ABS, (2 * vabs * verr + verr * verr).sum(red)))
+    return {"sum": (v.sum(red), ps), "sumsq": (sq, pq)}
+
+
+def assert_post_close(s, g, xhat, xmag, cap, probes=(), msg="", gerr=None):
+    """the backward sums of a BatchNorm, s[0] = sum g and s[1] = sum g * xhat over every dimension but the last.  g: float64, the
+    values the kernel sums; xhat = (y - mean) * rstd and xmag = (|y| + |mean|) * rstd in float64, from the kernel's fp32 tables or
+    from the float64 statistics those tables round (2^-24 of |mean| rstd and of rstd: inside the + 8 on xmag);
+    gerr: bound of g's own error where the kernel forms g; probes: [(name, f)], f(t) = the rows a wrong kernel would have summed"""
+    red = tuple(range(g.dim() - 1))
+    cnt = g[..., 0].numel()
+    p0, p1 = [(cnt, g.abs().sum(red))], [(cnt, (g.abs() * xmag).sum(red))]
+    if gerr is not None:
+        p0.append((ABS, gerr.sum(red))); p1.append((ABS, (gerr * xmag).sum(red)))
+    assert_sum_close(s[0], g.sum(red), p0, msg + "sum g", [(n, f(g).sum(red)) for n, f in probes], cap)
+    assert_sum_close(s[1], (g * xhat).sum(red), p1, msg + "sum g*xhat", [(n, (f(g) * f(xhat)).sum(red)) for n, f in probes], cap)
+
+
+def assert_stats_close(s, v, vabs, K, cnt, cap, verr=None, probes=(), msg=""):
+    """s[0] / s[1]: a kernel's sum / sum of squares; probes: [(name, f)] with f(v) = the values a wrong kernel would have summed"""
+    for i, (key, (want, parts)) in enumerate(stat_parts(v, vabs, K, cnt, verr).items()):
+        red = tuple(range(v.dim() - 1))
+        pr = [(n, f(v).sum(red) if i == 0 else (f(v) ** 2).sum(red)) for n, f in probes]
+        assert_sum_close(s[i], want, parts, f"{msg}{key}", pr, cap)

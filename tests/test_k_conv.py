@@ -3,7 +3,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from backends import be, be_gpu, DT, assert_close  # noqa: F401
+from backends import be, be_gpu, DT, ABS, assert_close, assert_sum_close, assert_stats_close, assert_post_close, pro_operand, stat_parts  # noqa: F401
 from mds import cabi, geometry as geo
 from oracle.multidim_stacker_ref import Conv2dSame
 
@@ -27,7 +27,7 @@ def ref_conv(x, w, stride):
     ref_mod = Conv2dSame(w.shape[1], w.shape[0], 3, stride, bias=False)   # the oracle's padding rule
     with torch.no_grad():
         probe = torch.zeros(1, w.shape[1], x.shape[2], x.shape[3])
-        assert ref_mod(probe).shape[2:] == F.conv2d(F.pad(probe, (pl, pr, pt, pb)), w.detach(), None, stride).shape[2:]
+        assert ref_mod(probe).shape[2:] == F.conv2d(F.pad(probe, (pl, pr, pt, pb)).to(w.dtype), w.detach(), None, stride).shape[2:]
     return F.conv2d(F.pad(x, (pl, pr, pt, pb)), w, None, stride)
 
 
@@ -37,6 +37,32 @@ def pack(w, kind, tdt):
     if kind == "oi":
         return w9.permute(0, 2, 1).contiguous().to(tdt)          # [O][9][I]
     return w9.flip(2).permute(1, 2, 0).contiguous().to(tdt)      # [I][9 flipped][O]
+
+
+def pro_ref(x, mode, scale, shift, dt):
+    """(a, err): the operand the kernel multiplies, in float64 - the stored x through the prologue, rounded to bf16 where the bf16
+    kernels round it - and the bound of its own error (backends.pro_operand; None without a prologue: x is held exactly)"""
+    xq = x.double()
+    if not mode:
+        return xq, None
+    sc, sh = scale.double().view(1, -1, 1, 1), shift.double().view(1, -1, 1, 1)
+    return pro_operand(xq * sc + sh, (xq * sc).abs() + sh.abs(), mode == 2, dt)
+
+
+def stat_probes(v):
+    """wrong sums over [N][OH][OW][C] at a statistics epilogue's seams: the ragged last band of 32 columns (exact bands: the last
+    eighth of the columns - one column of a K = 432 layer is below the resolution of `sumsq`), a row, the image boundary"""
+    W = v.shape[2]
+    nc = (W % 32 if W > 32 else 0) or max(1, W // 8)
+    pr = [(f"last {nc} columns left out", lambda t: t[:, :, :-nc]), ("row 0 counted twice", lambda t: torch.cat([t, t[:, :1]], 1))]
+    return pr + ([("last image left out", lambda t: t[:-1])] if v.shape[0] > 1 else [("last row left out", lambda t: t[:, :-1])])
+
+
+def wgrad64(a, dyt, shape, stride):
+    """float64 autograd of the convolution's filter (a: NCHW operand, dyt: NCHW output gradient)"""
+    ww = torch.zeros(shape, dtype=torch.float64, requires_grad=True)
+    ref_conv(a, ww, stride).backward(dyt)
+    return ww.grad
 
 
 CASES = [  # N, H, W, Cin, Cout, stride, pro
@@ -49,7 +75,7 @@ CASES = [  # N, H, W, Cin, Cout, stride, pro
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("N,H,W,Cin,Cout,stride,mode", CASES)
-def test_conv_fwd(be, dt, N, H, W, Cin, Cout, stride, mode):
+def test_conv_fwd(be, dt, N, H, W, Cin, Cout, stride, mode, probes=True):
     code, tdt = DT[dt]
     g = gen(H * W + Cin)
     x = torch.randn(N, Cin, H, W, generator=g).to(tdt)
@@ -65,20 +91,15 @@ def test_conv_fwd(be, dt, N, H, W, Cin, Cout, stride, mode):
                      pro=cabi.pro(mode, be.t(scale), be.t(shift)), residual=None, stats=st)
     be.call("conv_fwd", args)
     be.sync()
-    a = x.float()
-    if mode:
-        a = a * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
-        if mode == 2:
-            a = F.silu(a)
-        if dt == "bf16":
-            a = a.to(tdt).float()
-    ref = nhwc(ref_conv(a, w.float(), stride))
+    a, aerr = pro_ref(x, mode, scale, shift, dt)
+    ref = nhwc(ref_conv(a, w.double(), stride))
     assert ref.shape == y.shape
     assert_close(y, ref, dt, msg="y")
-    s = st.sum(0).cpu()
+    # the statistics are sums of the fp32 accumulators, before the store rounds them
+    vabs = nhwc(ref_conv(a.abs(), w.double().abs(), stride))
+    verr = nhwc(ref_conv(aerr, w.double().abs(), stride)) if mode else None
     cnt = N * OH * OW
-    assert_close(s[0], ref.sum((0, 1, 2)), dt, scale=cnt ** 0.5, msg="sum")
-    assert_close(s[1], (ref * ref).sum((0, 1, 2)), dt, scale=cnt ** 0.5, msg="sumsq")
+    assert_stats_close(st.sum(0), ref, vabs, 9 * Cin, cnt, (dt, cnt ** 0.5), verr, stat_probes(ref) if probes else ())
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -202,15 +223,15 @@ def test_conv_wgrad(be, dt, N, H, W, Cin, Cout, stride, mode):
     scale = 1 + 0.2 * torch.randn(Cin, generator=g); shift = 0.3 * torch.randn(Cin, generator=g)
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
     dyt = torch.randn(N, Cout, OH, OW, generator=g).to(tdt)
-    a = x.float()
-    if mode:
-        a = a * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
-        if mode == 2:
-            a = F.silu(a)
-        if dt == "bf16":
-            a = a.to(tdt).float()
-    ww = torch.zeros(Cout, Cin, 3, 3, requires_grad=True)
-    ref_conv(a, ww, stride).backward(dyt.float())
+    a, aerr = pro_ref(x, mode, scale, shift, dt)
+    shape, dy64 = (Cout, Cin, 3, 3), dyt.double()
+    want = wgrad64(a, dy64, shape, stride)
+    cnt = N * OH * OW
+    parts = [(cnt, wgrad64(a.abs(), dy64.abs(), shape, stride))] + ([(ABS, wgrad64(aerr, dy64.abs(), shape, stride))] if mode else [])
+    cut = dy64.clone(); cut[:, :, :, -1] = 0
+    probes = [("last output column left out", wgrad64(a, cut, shape, stride)), ("ky / kx transposed", want.transpose(2, 3))]
+    if N > 1:
+        probes.append(("last image left out", wgrad64(a[:-1], dy64[:-1], shape, stride)))
     dy, dx, wi = geo.taps_fwd(pt, pl)
     dw = be.out((Cout, Cin, 3, 3), torch.float32, 0, name="dw")
     be.call("conv_wgrad", cabi.make("mds_conv_wgrad_args", dtype=code, N=N, IH=H, IW=W, Cin=Cin, OH=OH, OW=OW,
@@ -218,7 +239,7 @@ def test_conv_wgrad(be, dt, N, H, W, Cin, Cout, stride, mode):
                                     x=be.t(nhwc(x)), dyt=be.t(nhwc(dyt)), dw=dw,
                                     pro=cabi.pro(mode, be.t(scale), be.t(shift))))
     be.sync()
-    assert_close(dw, ww.grad, dt, scale=(N * OH * OW) ** 0.5, msg="dw")
+    assert_sum_close(dw, want, parts, "dw", probes, cap=(dt, cnt ** 0.5))
 
 
 C3_CASES = [  # N, H, W, Cin, Cout, residual, statistics, block cap (0 = default grid)
@@ -233,6 +254,7 @@ C3_CASES = [  # N, H, W, Cin, Cout, residual, statistics, block cap (0 = default
     (1, 20, 50, 48, 192, False, True, 2),
     (2, 9, 70, 16, 32, False, False, 0),       # blocks.0.0's data gradient: 16 input channels (half-empty second k-step), 64-column bands
     (1, 17, 130, 16, 32, True, False, 3),
+    (2, 23, 37, 32, 128, False, True, 3),      # two images AND a ragged band AND several items per block: what a mis-masked statistics epilogue needs
 ]
 
 
@@ -259,11 +281,10 @@ def test_c3_filter_in_registers(be, N, H, W, Cin, Cout, res, stats, blocks):
     finally:
         be.lib.fn["dev_set"](cabi.MDS_KNOB_C3, 0)
         be.lib.fn["dev_set"](cabi.MDS_KNOB_CONV_BLOCKS, 0)
-    ref = nhwc(ref_conv(x.float(), w.float(), 1))
+    ref = nhwc(ref_conv(x.double(), w.double(), 1))
     if stats:
-        s = st.sum(0).cpu()
-        assert_close(s[0], ref.sum((0, 1, 2)), "bf16", scale=(N * H * W) ** 0.5, msg="sum")
-        assert_close(s[1], (ref * ref).sum((0, 1, 2)), "bf16", scale=(N * H * W) ** 0.5, msg="sumsq")
+        vabs = nhwc(ref_conv(x.double().abs(), w.double().abs(), 1))
+        assert_stats_close(st.sum(0), ref, vabs, 9 * Cin, N * H * W, ("bf16", (N * H * W) ** 0.5), None, stat_probes(ref))
     if res:
         ref = ref + r.float()
     assert_close(y, ref, "bf16", msg="y")
@@ -345,12 +366,12 @@ def test_c3_post_statistics(be, stride, N, H, W, blocks, masked, Cin, Cout):
         ref = ref.to(tdt).float() * (sg * (1 + z * (1 - sg)))
     assert_close(dxo, ref, "bf16", msg="dx")
     u = dxo.float().cpu()                                   # the sums are taken of what later readers will read
-    gg = u * (mask.view(N, 1, 1, 1) if masked else 1.0)
-    xhat = (yb.float() - bn[2]) * bn[3]
-    s = st.sum(0).cpu()
-    cnt = N * H * W
-    assert_close(s[0], gg.sum((0, 1, 2)), "bf16", scale=cnt ** 0.5, msg="sum g")
-    assert_close(s[1], (gg * xhat).sum((0, 1, 2)), "bf16", scale=cnt ** 0.5, msg="sum g xhat")
+    gg = u.double() * (mask.double().view(N, 1, 1, 1) if masked else 1.0)
+    b64 = bn.double()
+    xhat, xmag = (yb.double() - b64[2]) * b64[3], (yb.double().abs() + b64[2].abs()) * b64[3].abs()
+    probes = [("last column left out", lambda t: t[:, :, :-1]), ("row 0 counted twice", lambda t: torch.cat([t, t[:, :1]], 1))]
+    probes.append(("first image left out", lambda t: t[1:]) if N > 1 else ("last row left out", lambda t: t[:, :-1]))
+    assert_post_close(st.sum(0), gg, xhat, xmag, ("bf16", (N * H * W) ** 0.5), probes)
     # the old kernels refuse post statistics instead of ignoring them
     be.lib.check(be.lib.fn["dev_set"](cabi.MDS_KNOB_C3, 1), "dev_set")
     try:
@@ -423,6 +444,7 @@ C3S_CASES = [  # N, H, W (even: TF-SAME pads 0 / 1), Cin, Cout, prologue mode, b
     (1, 26, 256, 16, 64, 2, 2),       # ... two blocks walk several items; the pad column (W) and row (H) are zero AFTER the activation
     (1, 4, 128, 16, 64, 2, 1),
     (1, 26, 100, 16, 64, 2, 2),       # a ragged width behind the prologue is refused (k_conv.hip takes it): same answer
+    (2, 22, 40, 32, 128, 0, 2),       # two images, ragged band (20 output columns), two blocks walk several items
 ]
 
 
@@ -446,6 +468,7 @@ C3W_CASES = [  # N, H, W, Cin, Cout, block cap
     (1, 20, 50, 48, 192, 2),
     (1, 3, 32, 32, 128, 1),        # fewer rows than the ring is deep
     (1, 1, 16, 48, 192, 0),        # a single image row: one input row between two zero entries
+    (2, 23, 37, 32, 128, 3),       # two images, ragged band, several items per block at once
 ]
 
 
@@ -534,10 +557,43 @@ def test_k_c3_at_the_training_sizes_against_k_conv(be_gpu, H, W, Cin, Cout, stri
     (y0, s0, w0), (y1, s1, w1) = out[0], out[1]
     assert not torch.isnan(y0.float()).any()
     assert_close(y0, y1, "bf16", msg="y")
-    cnt = N * OH * OW
-    assert_close(s0[0], s1[0], "bf16", scale=cnt ** 0.5, msg="sum")
-    assert_close(s0[1], s1[1], "bf16", scale=cnt ** 0.5, msg="sumsq")
-    assert_close(w0, w1, "bf16", scale=cnt ** 0.5, msg="dw")
+    # The sums: each kernel against the other within the SUM of both a-priori bounds.  The magnitudes come from torch in float32 on
+    # the device (they need percent accuracy).  Chains: a lane adds one accumulator per pixel it owns over the block's whole life
+    # (k_c3.hip `ps[c2] += v`, k_conv.hip `ps[nf * 4 + r] += v[r]`), 16 lanes share a block's pixels, a block owns at most twice
+    # the average share (c3_split: ceil(items / blocks) <= 2 items / blocks), the grids have one block per CU and 64-channel pass;
+    # + 16 for the cross-lane reduction.  The weight gradient's accumulators take every pixel of the block: 16 times that chain.
+    cnt, dev = N * OH * OW, be.device
+    sc64, sh64 = scale.double().view(1, -1, 1, 1), shift.double().view(1, -1, 1, 1)
+    xc = x.permute(0, 3, 1, 2)
+    if mode:
+        z = xc.double() * sc64 + sh64
+        a, aerr = pro_operand(z, (xc.double() * sc64).abs() + sh64.abs(), mode == 2, "bf16")
+        a, aerr = a.float(), aerr.float()
+        del z
+    else:
+        a, aerr = xc.float(), None
+    (p0, p1), (q0, q1) = (geo.same_pad(H, stride), geo.same_pad(W, stride)) if stride == 2 else ((1, 1), (1, 1))
+    conv = lambda t, f: F.conv2d(F.pad(t, (q0, q1, p0, p1)), f, None, stride).permute(0, 2, 3, 1)      # noqa: E731
+    wf = w.float()
+    v, vabs = conv(a, wf), conv(a.abs(), wf.abs())
+    verr = conv(aerr, wf.abs()) if mode else None
+    lane = 2 * -(-cnt * -(-Cout // 64) // (16 * torch.cuda.get_device_properties(dev).multi_processor_count)) + 16
+    img = v[-1:]                                                # probe: the last image left out of the sums
+    for i, (key, (_, parts)) in enumerate(stat_parts(v, vabs, 9 * Cin, lane, verr).items()):
+        gone = (img if i == 0 else img * img).sum((0, 1, 2)).double()
+        # (a zero-mean layer's per-image SUM, sqrt(OH * OW) rms, is below the bound of a chain this long: no probe there)
+        probes = [("last image left out", s1[i] - gone)] if (i == 1 or mode == 2) else []
+        assert_sum_close(s0[i], s1[i], parts + parts, key, probes, cap=("bf16", cnt ** 0.5))
+
+    def wg(t, d):
+        ww = torch.zeros(Cout, Cin, 3, 3, device=dev, requires_grad=True)
+        F.conv2d(F.pad(t, (q0, q1, p0, p1)), ww, None, stride).backward(d.permute(0, 3, 1, 2))
+        return ww.grad
+    dyf = dyt.float()
+    parts = [(16 * lane, wg(a.abs(), dyf.abs()))] + ([(ABS, wg(aerr, dyf.abs()))] if mode else [])
+    # (no probe: with every product counted as one addition of the chain - the matrix unit's inner order is not documented - the
+    # bound at this size exceeds one image's share; the small shapes above carry the weight gradient's probes)
+    assert_sum_close(w0, w1, parts + parts, "dw", cap=("bf16", cnt ** 0.5))
 
 
 def _rand_cases(n, seed):
@@ -560,7 +616,7 @@ def test_conv_fwd_random_shapes(be_gpu, dt, N, H, W, Cin, Cout, stride, mode, bl
     is too slow for 32 random layers)"""
     be = be_gpu
     be.lib.check(be.lib.fn["dev_set"](cabi.MDS_KNOB_CONV_BLOCKS, blocks), "dev_set")
-    try:
-        test_conv_fwd(be, dt, N, H, W, Cin, Cout, stride, mode)
+    try:      # (no probes: up to 18 900 pixels - there the bound of `sum` exceeds a column of zero-mean values; the fixed small cases carry them)
+        test_conv_fwd(be, dt, N, H, W, Cin, Cout, stride, mode, probes=False)
     finally:
         be.lib.fn["dev_set"](cabi.MDS_KNOB_CONV_BLOCKS, 0)

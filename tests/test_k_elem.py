@@ -3,7 +3,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from backends import be, DT, assert_close  # noqa: F401
+from backends import be, DT, ABS, U, assert_close, assert_sum_close, assert_post_close, pro_operand  # noqa: F401
 from mds import cabi
 
 SLOTS = cabi.MDS_STAT_SLOTS
@@ -20,6 +20,136 @@ def bn_finalize(be, stats, count, gamma, beta, eps=1e-3, momentum=0.1, training=
                                      beta=beta, eps=eps, momentum=momentum, training=training,
                                      running_mean=rm, running_var=rv, num_batches_tracked=nbt, out=out))
     return out
+
+
+F64 = torch.float64
+
+
+def silu_grad64(z, zmag):
+    """(silu'(z), silu'(z) on magnitudes, bound of the error of the kernels' fp32 evaluation): s (1 + z (1 - s)) through v_exp / v_rcp
+    is (|z| + 12) U of its magnitude off (the reasoning of backends.pro_operand), and z's own rounding U * zmag moves it by at most
+    |silu''| <= 1/2 times that (z: two roundings on fp32-rounded tables, 2 U * zmag)"""
+    s = torch.sigmoid(z)
+    mag = s * (1 + z.abs() * (1 - s))
+    return s * (1 + z * (1 - s)), mag, U * ((z.abs() + 12) * mag + zmag)
+
+
+def check_bn_bwd_sums(dgamma, dbeta, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, dt, running=None):
+    """dbeta = sum g and dgamma = sum g * xhat of mds_bn_bwd_reduce / _finalize against their float64 values on the stored y and u,
+    g formed as mds_gsrc_t says; bound: the fp32 sum over M rows + the error of g where the kernel computes a SiLU factor.
+    xhat comes from the float64 mean / rstd of y, which the kernels' fp32 table rounds (see backends.assert_post_close).
+    Probes at the row loops' seams: the last rows (a ragged last trip) left out / taken twice, in a DropPath group that is kept."""
+    M, C = y.shape
+    y64, u64, grp = y.to(F64), u.to(F64), torch.arange(M) // rpg
+    if running is None:
+        mean, var = y64.mean(0), y64.var(0, unbiased=False)
+    else:
+        mean, var = running[0].to(F64), running[1].to(F64)
+    rstd = 1 / torch.sqrt(var + eps)
+    sc = gamma.to(F64) * rstd
+    sh = beta.to(F64) - mean * sc
+    z, zmag = y64 * sc + sh, (y64 * sc).abs() + sh.abs()
+    src, smag = u64, u64.abs()
+    if mode == cabi.MDS_G_SE_SILU:
+        src, smag = u64 * gate.to(F64)[grp] + dpool.to(F64)[grp], (u64 * gate.to(F64)[grp]).abs() + dpool.to(F64)[grp].abs()
+    if mode == cabi.MDS_G_MASK:
+        src, smag = u64 * mask.to(F64)[grp, None], smag * mask.to(F64)[grp, None].abs()
+    gerr = None
+    if mode in (cabi.MDS_G_SILU, cabi.MDS_G_SE_SILU):
+        d, dmag, derr = silu_grad64(z, zmag)
+        src, gerr = src * d, smag * derr + 2 * U * smag * dmag
+    xhat, xmag = (y64 - mean) * rstd, (y64.abs() + mean.abs()) * rstd
+    r, end = M % 32 + 16, M
+    if mode == cabi.MDS_G_MASK:     # the rows up to the end of the last group DropPath keeps
+        end = min(M, (int(mask.nonzero().max()) + 1) * rpg)
+    keep = torch.cat([torch.arange(end - r), torch.arange(end, M)])
+    probes = [(f"rows {end - r}..{end - 1} left out", lambda t: t[keep]), (f"rows {end - r}..{end - 1} counted twice", lambda t: torch.cat([t, t[end - r:end]], 0))]
+    assert_post_close(torch.stack([dbeta.detach().double().cpu(), dgamma.detach().double().cpu()]), src, xhat, xmag, (dt, 20),
+                      probes if M <= 3000 else (), "dbeta / dgamma: ", gerr)
+
+
+def se_backward64(dgate, gate, hidden, pooled, w1, w2, drop_c=0):
+    """the parameter gradients of mds_se_fc_bwd in float64 from ITS operands - the dgate, gate, hidden and pooled buffers the
+    launches before it left - with their a-priori bounds: {name: (want, parts)}.  dpre = dgate * gate (1 - gate);
+    db2 = sum_g dpre, dw2 = sum_g dpre (x) silu(hidden); dh = dpre W2 (a sum over the C channels), dhid = dh * silu'(hidden);
+    db1 = sum_g dhid, dw1 = sum_g dhid (x) pooled.  silu / silu' through v_exp / v_rcp: 12 U of their magnitude (the reasoning of
+    backends.pro_operand); the sum over C is inherited by dw1 / db1 as an absolute part.  drop_c: a probe - the last drop_c
+    channels left out of the sum over C.  The chains, none of them fitted:
+      db2: G additions; a term dgate * gate * (1 - gate) is 1 - gate, two products and the fp64 -> fp32 conversion of dgate: 4
+      roundings more than the helper's + 8 allows for one product, hence G + 4;
+      dw2: the same term times silu(hidden): 12 more for silu through v_exp / v_rcp and 4 as above, hence G + 16;
+      dhid: C additions for dh, + 8 for the term dpre * w2 (as db2's, itself 4 + the product: within 8), + 16 for
+      silu'(hidden) = s (1 + hid (1 - s)): 12 for the sigmoid as in pro_operand and 4 roundings of the polynomial, hence C + 8 + 16."""
+    G, C = gate.shape
+    dg, gt, hid, pl, W1, W2 = (t.detach().to(F64).cpu() for t in (dgate, gate, hidden, pooled, w1, w2))
+    s = torch.sigmoid(hid)
+    h, dh_ = hid * s, s * (1 + hid * (1 - s))
+    dh_m = s * (1 + hid.abs() * (1 - s))
+    dpre = dg * gt * (1 - gt)
+    keep = C - drop_c
+    dh, dhm = dpre[:, :keep] @ W2[:keep], dpre[:, :keep].abs() @ W2[:keep].abs()
+    dhid, dhid_m = dh * dh_, dhm * dh_m
+    dhid_e = (C + 8 + 16) * U * dhid_m
+    return {"db2": (dpre.sum(0), [(G + 4, dpre.abs().sum(0))]),
+            "dw2": (dpre.t() @ h, [(G + 16, dpre.abs().t() @ h.abs())]),
+            "db1": (dhid.sum(0), [(G, dhid_m.sum(0)), (ABS, dhid_e.sum(0))]),
+            "dw1": (dhid.t() @ pl, [(G, dhid_m.t() @ pl.abs()), (ABS, dhid_e.t() @ pl.abs())])}
+
+
+def check_se_backward(got, bufs, y, scale, shift, w1, w2, u, G, R_, dt):
+    """got: {name: kernel output}: dgate [G][C] = the sum over a group's R_ rows of u * a, a = silu(y * scale + shift) held in
+    fp32, and the four parameter gradients (se_backward64 on bufs = the kernels' own dgate, gate, hidden, pooled).
+    Probes: the last group left out; the first group taken twice (dw2 / db2); the last 8 channels left out of the sum over C
+    (dw1 / db1); for dgate the last 6 rows of every group left out"""
+    C = w1.shape[1]
+    y64, sc, sh = y.to(F64), scale.to(F64), shift.to(F64)
+    a, aerr = pro_operand(y64 * sc + sh, (y64 * sc).abs() + sh.abs(), True, "f32")
+    ua, ue = (u.to(F64) * a).view(G, R_, C), (u.to(F64).abs() * aerr).view(G, R_, C)
+    cutg = ua.clone(); cutg[-1] = 0
+    assert_sum_close(got["dgate"], ua.sum(1), [(R_, ua.abs().sum(1)), (ABS, ue.sum(1))], "dgate",
+                     [("last group left out", cutg.sum(1)), ("last 6 rows of every group left out", ua[:, :-6].sum(1))], cap=(dt, R_ ** 0.5))
+    ref = se_backward64(w1=w1, w2=w2, **bufs)
+    zero_last = dict(bufs, dgate=torch.cat([bufs["dgate"][:-1], torch.zeros_like(bufs["dgate"][-1:])]))
+    twice = {k: torch.cat([v, v[:1]]) for k, v in bufs.items()}
+    wrong = {"last group left out": se_backward64(w1=w1, w2=w2, **zero_last), "first group counted twice": se_backward64(w1=w1, w2=w2, **twice),
+             "last 8 channels left out of the sum over C": se_backward64(w1=w1, w2=w2, drop_c=8, **bufs)}
+    for name in ("dw1", "db1", "dw2", "db2"):
+        want, parts = ref[name]
+        names = ["last group left out", "first group counted twice" if name in ("dw2", "db2") else "last 8 channels left out of the sum over C"]
+        assert_sum_close(got[name], want, parts, name, [(n, wrong[n][name][0]) for n in names], cap=(dt, 10))
+
+
+def gem_dp64(y, scale, shift, pro_mode, p, dpo, G, R_, eps):
+    """GeM's dp = d/dp sum(dpooled * pooled), pooled = (mean_r x^p)^(1/p), x = max(a, eps), in float64: per (group, channel)
+    dpooled * pooled * [T / (p S) - ln(S / R) / p^2] with S = sum_r x^p, T = sum_r x^p ln x.  -> (want [1], parts).
+    Bound: the fp32 chain over R_ rows and over the G * C terms, the power x^p = exp2(p log2 x) (v_log / v_exp: 1 ulp each, the
+    rounded exponent moves it by p |ln x| U), p times the activation's own error ((|z| + 4) U, backends.pro_operand), + 32 =
+    four more transcendental evaluations at 8 U each (log2 and exp2 of a term's power: 1 ulp + argument and result roundings;
+    the root (S / R)^(1 / p), again a log2 / exp2 pair; ln(S / R)); on magnitudes: |ln x| for ln x, and |ln(S / R)| + 1 because S's relative error is an
+    ABSOLUTE error of its logarithm."""
+    C, y = y.shape[1], y.detach()
+    z = y.to(F64) * scale.to(F64) + shift.to(F64) if pro_mode else y.to(F64)
+    a = z * torch.sigmoid(z) if pro_mode else z
+    x = a.clamp(min=eps).view(G, R_, C)
+    pw, lx = x.pow(p), x.log()
+    S, T, Tm = pw.sum(1), (pw * lx).sum(1), (pw * lx.abs()).sum(1)
+    pooled = (S / R_).pow(1 / p)
+    d64 = dpo.to(F64)
+    want = (d64 * pooled * (T / (p * S) - (S / R_).log() / p ** 2)).sum().view(1)
+    mag = (d64.abs() * pooled * (Tm / (p * S) + ((S / R_).log().abs() + 1) / p ** 2)).sum().view(1)
+    chain = R_ + G * C + p * (float(lx.abs().max()) + (float(z.abs().max()) + 4 if pro_mode else 0)) + 32
+    return want, [(chain, mag)]
+
+
+def check_gem_dp(dp, y, scale, shift, pro_mode, p, dpo, G, R_, eps, dt):
+    """probes: the last group left out; the last eighth of every group's rows left out"""
+    want, parts = gem_dp64(y, scale, shift, pro_mode, p, dpo, G, R_, eps)
+    cut = dpo.clone(); cut[-1] = 0
+    k = max(1, R_ // 8)
+    rows = y.view(G, R_, -1)[:, :-k].reshape(G * (R_ - k), -1)
+    probes = [("last group left out", gem_dp64(y, scale, shift, pro_mode, p, cut, G, R_, eps)[0]),
+              (f"last {k} rows of every group left out", gem_dp64(rows, scale, shift, pro_mode, p, dpo, G, R_ - k, eps)[0])]
+    assert_sum_close(dp, want, parts, "dp", probes, cap=(dt, 5))
 
 
 def test_bn_finalize_train_and_eval(be):
@@ -126,8 +256,8 @@ def test_se_forward_backward(be, dt, packed, C, RD):
     be.sync()
     assert_close(pooled, pooled_ref, dt, msg="pooled")
     assert_close(gate, gate_ref, dt, msg="gate")
-    assert_close(dw1, p["w1"].grad, dt, scale=10, msg="dw1"); assert_close(db1, p["b1"].grad, dt, scale=10, msg="db1")
-    assert_close(dw2, p["w2"].grad, dt, scale=10, msg="dw2"); assert_close(db2, p["b2"].grad, dt, scale=10, msg="db2")
+    check_se_backward(dict(dgate=dgate, dw1=dw1, db1=db1, dw2=dw2, db2=db2), dict(dgate=dgate, gate=gate, hidden=hidden, pooled=pooled),
+                      y, scale, shift, w1, w2, u, G, R_, dt)
     # total grad wrt a = u*gate + dpooled(broadcast): check through the BN-backward g-source
     da_ref = a.grad.view(M, C)
     da = ud.float().cpu() * gate.cpu()[torch.arange(M) // R_] + dpooled.cpu()[torch.arange(M) // R_]
@@ -209,8 +339,7 @@ def test_bn_backward_chain(be, dt, mode, C):
     dy = be.out((M, C), tdt, float("nan"))
     be.call("bn_bwd_apply", cabi.make("mds_bn_bwd_apply_args", dtype=code, M=M, C=C, g=gs, y=yd, bn=bn, coef=coef, dy=dy))
     be.sync()
-    assert_close(dgamma, gam.grad, dt, scale=20, msg="dgamma")
-    assert_close(dbeta, bet.grad, dt, scale=20, msg="dbeta")
+    check_bn_bwd_sums(dgamma, dbeta, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, dt)
     assert_close(dy, yf.grad, dt, scale=2, msg="dy")
 
 
@@ -287,8 +416,7 @@ def test_bn_backward_chain_fp64_means(be, mode):
     _, y, u, gamma, beta, gate, dpool, mask = _bn_bwd_inputs(M, C, rpg, torch.float32, 61 + mode)
     dy_ref, dgamma_ref, dbeta_ref = bn_bwd_reference(y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps)
     dy, dgamma, dbeta, _, _ = _bn_bwd_chain(be, "f32", y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, use64=True)
-    assert_close(dgamma, dgamma_ref, "f32", scale=20, msg="dgamma")
-    assert_close(dbeta, dbeta_ref, "f32", scale=20, msg="dbeta")
+    check_bn_bwd_sums(dgamma, dbeta, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, "f32")
     assert_close(dy, dy_ref, "f32", scale=2, msg="dy")
 
 
@@ -309,7 +437,7 @@ def test_bn_backward_fp64_means_keep_the_column_sums(be):
     for use64 in (False, True):
         dy, dgamma, dbeta, _, _ = _bn_bwd_chain(be, "f32", y, u, gamma, beta, 0, None, None, None, rpg, eps, use64=use64)
         assert_close(dy, dy_ref, "f32", scale=2, msg=f"dy (coef64: {use64})")
-        assert_close(dgamma, dgamma_ref, "f32", scale=20, msg="dgamma"); assert_close(dbeta, dbeta_ref, "f32", scale=20, msg="dbeta")
+        check_bn_bwd_sums(dgamma, dbeta, y, u, gamma, beta, 0, None, None, None, rpg, eps, "f32")
         err[use64] = float((dy.cpu().double().sum(0) - dy_ref.sum(0)).abs().max())
     assert err[True] <= err[False], f"worst column sum of dy: {err[True]:.3e} off the float64 sum with coef64, {err[False]:.3e} without"
 
@@ -326,8 +454,7 @@ def test_bn_backward_eval_mode(be, dt, mode):
     rm = 0.3 + 0.2 * torch.randn(C, generator=g); rv = 1.5 + torch.rand(C, generator=g)
     dy_ref, dgamma_ref, dbeta_ref = bn_bwd_reference(y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, running=(rm, rv))
     dy, dgamma, dbeta, coef, lin = _bn_bwd_chain(be, dt, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, running=(rm, rv))
-    assert_close(dgamma, dgamma_ref, dt, scale=20, msg="dgamma")
-    assert_close(dbeta, dbeta_ref, dt, scale=20, msg="dbeta")
+    check_bn_bwd_sums(dgamma, dbeta, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, dt, running=(rm, rv))
     assert_close(dy, dy_ref, dt, scale=2, msg="dy")
     A = gamma.double() / torch.sqrt(rv.double() + eps)
     assert_close(coef[0], A, "f32", msg="coef0"); assert_close(lin[0], A, "f32", msg="A")
@@ -362,7 +489,7 @@ def test_gem_fwd_bwd(be, dt, pro_mode, split, R_, C, golden):
     be.sync()
     assert_close(pooled, pooled_ref, dt, msg="pooled")
     assert_close(u, a.grad, dt, msg="u")
-    assert_close(dp, pp.grad, dt, scale=5, msg="dp")
+    check_gem_dp(dp, y, scale, shift, pro_mode, 3.0, dpo, G, R_, 1e-6, dt)
 
 
 def test_gem_matches_reference_golden(be, golden):
@@ -386,7 +513,8 @@ def test_gem_matches_reference_golden(be, golden):
     assert_close(pooled[:, :C], torch.from_numpy(d["y"]), "f32", msg="y")
     dx = u.cpu()[:, :C].view(B, H, W, C).permute(0, 3, 1, 2)
     assert_close(dx, torch.from_numpy(d["dx"]), "f32", msg="dx")
-    assert_close(dp, torch.from_numpy(d["dp"]), "f32", scale=5, msg="dp")
+    assert_close(gem_dp64(rows, None, None, 0, 3.0, dpo, B, H * W, 1e-6)[0], torch.from_numpy(d["dp"]), "f32", msg="the float64 dp is the reference class's")
+    check_gem_dp(dp, rows, None, None, 0, 3.0, dpo, B, H * W, 1e-6, "f32")
 
 
 def test_head_fwd_bwd(be):

@@ -17,8 +17,9 @@ import torch.nn.functional as F
 
 import test_k_conv
 import test_k_dw_stem
-from test_k_elem import bn_bwd_reference
-from backends import be, DT, assert_close, knobs  # noqa: F401
+import test_k_pw
+from test_k_elem import bn_bwd_reference, check_bn_bwd_sums, check_se_backward, silu_grad64
+from backends import be, DT, ABS, U, assert_close, assert_sum_close, assert_post_close, knobs  # noqa: F401
 from mds import cabi
 
 SLOTS = cabi.MDS_STAT_SLOTS
@@ -119,8 +120,7 @@ def test_bn_backward_chain_grid_stride_trips(be, dt, mode, C, M, cap):
         if ragged is not None and C == 40:
             assert ragged
     assert bool(torch.isnan(buf[M:].float()).all()), "bn_bwd_apply stored a row past M"
-    assert_close(dgamma, dgamma_ref, dt, scale=20, msg="dgamma")
-    assert_close(dbeta, dbeta_ref, dt, scale=20, msg="dbeta")
+    check_bn_bwd_sums(dgamma, dbeta, y, u, gamma, beta, mode, gate, dpool, mask, rpg, eps, dt)
     assert_close(dy, dy_ref, dt, scale=2, msg="dy")
 
 
@@ -217,19 +217,24 @@ def test_se_grouped_reduces_several_blocks_per_group(be, dt, C, RD):
     act64 = act.cpu().to(F64)
     assert_close(pooled_m, act64.view(G, R_, C).mean(1), dt, msg="pooled (materialised input)")
     assert_close(gate, gate_ref, dt, msg="gate")
-    # sums over the R_ rows of a group / the M rows of the tensor: the tolerance of the type times sqrt(number of terms), as every
-    # column-sum check of the kernel tests
-    assert_close(dgate, (u.to(F64) * a.detach()).view(G, R_, C).sum(1), dt, scale=R_ ** 0.5, msg="dgate (raw input)")
-    assert_close(dgate_m, (u.to(F64) * act64).view(G, R_, C).sum(1), dt, scale=R_ ** 0.5, msg="dgate (materialised input)")
-    assert_close(dw1, p["w1"].grad, dt, scale=10, msg="dw1"); assert_close(db1, p["b1"].grad, dt, scale=10, msg="db1")
-    assert_close(dw2, p["w2"].grad, dt, scale=10, msg="dw2"); assert_close(db2, p["b2"].grad, dt, scale=10, msg="db2")
+    # sums over the R_ rows of a group, the groups and the channels: float64 on the same operands + the fp32 summation bound
+    check_se_backward(dict(dgate=dgate, dw1=dw1, db1=db1, dw2=dw2, db2=db2), dict(dgate=dgate, gate=gate, hidden=hidden, pooled=pooled),
+                      y, scale, shift, w1, w2, u, G, R_, dt)
+    um = (u.to(F64) * act64).view(G, R_, C)
+    cutg = um.clone(); cutg[-1] = 0
+    assert_sum_close(dgate_m, um.sum(1), [(R_, um.abs().sum(1))], "dgate (materialised input)",
+                     [("last group left out", cutg.sum(1)), ("last 6 rows of every group left out", um[:, :-6].sum(1))], cap=(dt, R_ ** 0.5))
     grp = torch.arange(M) // R_
     da = u.to(F64) * gate.cpu().to(F64)[grp] + dpooled.cpu().to(F64)[grp]
     assert_close(da, da_ref, dt, scale=3, msg="da")
     s = bn_stats.sum(0).cpu()
     assert float(bn_stats[1:].abs().sum()) == 0.0, "se_fc_bwd adds the BatchNorm sums to slot 0"
-    assert_close(s[0], g_ref.sum(0), dt, scale=M ** 0.5, msg="sum g")
-    assert_close(s[1], (g_ref * xhat).sum(0), dt, scale=M ** 0.5, msg="sum g*xhat")
+    # g = (u * gate + dpooled) * silu'(z) from the KERNELS' gate and dpooled (checked above), so that the sums see the same operands
+    d, dmag, derr = silu_grad64(z, (y.to(F64) * scale.to(F64)).abs() + shift.to(F64).abs())
+    damag = (u.to(F64) * gate.cpu().to(F64)[grp]).abs() + dpooled.cpu().to(F64)[grp].abs()
+    xmag = (y.to(F64).abs() + mean.to(F64).abs()) * rstd.to(F64)
+    probes = [("last group left out", lambda t: t[:-R_]), ("first 16 rows counted twice", lambda t: torch.cat([t, t[:16]], 0))]
+    assert_post_close(s, da * d, xhat, xmag, (dt, M ** 0.5), probes, gerr=damag * derr + 4 * U * damag * dmag)
 
 
 # ------------------------------------------------------------------------------------------------ mds_pw_fwd
@@ -306,10 +311,11 @@ def test_pw_fwd_large_tiles(be, dt, M, N, gy, pmode, res, stats):
     if res:
         ref = ref + r.to(F64)
     assert_close(y, ref, dt, msg="y")
-    if stats:      # (the statistics are those of what is stored, residual included: as tests/test_k_pw.py)
-        s = st.sum(0).cpu()
-        assert_close(s[0], ref.sum(0), dt, scale=M ** 0.5, msg="sum")
-        assert_close(s[1], (ref * ref).sum(0), dt, scale=M ** 0.5, msg="sumsq")
+    if stats:      # (the statistics are those of the fp32 accumulators + residual, before the store: as tests/test_k_pw.py)
+        a, aerr = test_k_pw._pro64(x, pmode, scale, shift, gate, rpg, dt)
+        v = a @ w.to(F64).t() + r.to(F64)
+        vabs = a.abs() @ w.to(F64).abs().t() + r.to(F64).abs()
+        test_k_pw._check_stats(st, v, vabs, aerr @ w.to(F64).abs().t() if pmode else None, K + 1, M, dt)
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -349,10 +355,7 @@ def test_pw_fwd_large_tiles_data_gradient(be, dt, M, N, gy, gmode, res, post):
     stored = v * silu_grad(ys.to(F64) * b2[0] + b2[1]) if post == cabi.MDS_POST_SILU else v
     assert_close(out, stored, dt, scale=2, msg="out")
     gq = out.cpu().to(F64) * (mask2.to(F64)[grp, None] if post == cabi.MDS_POST_MASK else 1.0)   # the sums are defined on what was stored
-    xh = (ys.to(F64) - b2[2]) * b2[3]
-    s = st2.sum(0).cpu()
-    assert_close(s[0], gq.sum(0), "f32", scale=50 * M ** 0.5, msg="post sum g")
-    assert_close(s[1], (gq * xh).sum(0), "f32", scale=50 * M ** 0.5, msg="post sum g*xhat")
+    test_k_pw._check_post(st2, gq, ys, b2, M, C)
 
 
 def pw_epi_reference(x, w, r, pmode, scale, shift, gate, rpg, esc, esh, emode, tdt):
@@ -499,7 +502,11 @@ def test_pw_wgrad_block_budget(be, dt, budget, M, det):
         if budget == 4096:      # at these M the default budget ends at the same 256-row floor; where it does not, the knob must show
             big = cabi.make("mds_pw_wgrad_args", dtype=code, M=100000, K=K, N=N, pro=cabi.pro(0))
             assert int(be.lib.fn["pw_wgrad_partial_floats"](ctypes.byref(big))) // (N * K) == cdiv(100000, 256)
-    assert_close(outs[0], ref, dt, scale=M ** 0.5, msg="dw")
+    a, aerr = test_k_pw._pro64(x, pmode, scale, shift, gate, rpg, dt)
+    d64 = dy.to(F64)
+    r_, t_ = M % 256, M // 8       # (an eighth of the rows: 16 rows are below the bound's resolution at M = 5000)
+    probes = [(f"last {r_} rows (the ragged split) left out", d64[:-r_].t() @ a[:-r_]), (f"first {t_} rows counted twice", d64.t() @ a + d64[:t_].t() @ a[:t_])]
+    assert_sum_close(outs[0], d64.t() @ a, [(M, d64.abs().t() @ a.abs()), (ABS, d64.abs().t() @ aerr)], "dw", probes, cap=(dt, M ** 0.5))
     if det:
         assert torch.equal(outs[0], outs[1]), "two launches with a partial buffer must agree bit for bit"
 
@@ -526,7 +533,7 @@ def test_dw_grid_orders(be, dt, order, N, T, H, W, C, stride, kt):
     strip blocks in grid.y: out of reach of a quick test.)"""
     from test_deterministic_kernels import DetBackend
     with knobs(be, {cabi.MDS_KNOB_DW_ORDER: order}):
-        test_k_dw_stem._dw_fwd_bwd(DetBackend(be), dt, N, T, H, W, C, stride, kt, rd=F64)
+        test_k_dw_stem._dw_fwd_bwd(DetBackend(be), dt, N, T, H, W, C, stride, kt)
         ls = be.launches()
         if ls is not None:
             ls = [l for l in ls if re.search(r"dw2s?_|dw3g?_", l.kernel)]       # the launches that go through dw_grid
@@ -543,7 +550,7 @@ def test_dw3_tiled_forward_bf16(be, N, T, H, W, C, stride, kt):
     """dw_fwd_kernel<bf16_t, 1, 3>: the LDS-tiled 3x3x3 forward, which bf16 launches at T != 5 take only with MDS_KNOB_DW3G = 1
     (by default they take the time-chunked sliding window dw3g_fwd_kernel)"""
     with knobs(be, {cabi.MDS_KNOB_DW3G: 1}):
-        test_k_dw_stem._dw_fwd_bwd(be, "bf16", N, T, H, W, C, stride, kt, rd=F64)
+        test_k_dw_stem._dw_fwd_bwd(be, "bf16", N, T, H, W, C, stride, kt, act_rounded=True)
         ls = be.launches("_fwd_kernel")
         assert ls is None or (len(ls) == 1 and "dw_fwd_kernel" in ls[0].kernel and "dw3g" not in ls[0].kernel), ls
 
@@ -556,7 +563,7 @@ def test_dw2_strip_count_rule(be, dt):
     blocks = {}
     for target in (1, 100000):
         with knobs(be, {cabi.MDS_KNOB_DW2_BLOCKS: target}):
-            test_k_dw_stem._dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt, rd=F64)
+            test_k_dw_stem._dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt)
             ls = be.launches("dw2_")
             if ls is not None:
                 assert len(ls) == 2, ls
@@ -586,7 +593,7 @@ def test_stem_fwd_gather_kernel_bf16(be, N, H, W):
     """stem_fwd_kernel<bf16_t> without an output transform: the training forward takes the LDS-tiled kernel (stem_fwd_tiled)
     unless MDS_KNOB_STEM_FWD = 1; the gather kernel's raw bf16 output and its statistics, at the shapes of test_stem_fwd_wgrad"""
     with knobs(be, {cabi.MDS_KNOB_STEM_FWD: 1}):
-        test_k_dw_stem.test_stem_fwd_wgrad(be, "bf16", N, H, W, rd=F64)
+        test_k_dw_stem.test_stem_fwd_wgrad(be, "bf16", N, H, W)
         ls = be.launches("stem_fwd")
         assert ls is None or (len(ls) == 1 and ls[0].kernel.startswith("stem_fwd_kernel")), ls
 
