@@ -3,7 +3,9 @@
 //
 // Roofline: pure HBM streaming — a sample without spatial filter is read once (bilinear gathers of a near-identity affine
 // map: neighbouring lanes touch neighbouring source pixels, the re-use is served by L1/L2) and written once, 4 pixels
-// (16 bytes) per lane; algorithmic bytes = 2 x 4 B per pixel (+ the same again per extra filter pass of a sample).
+// (16 bytes) per lane; algorithmic bytes = 2 x 4 B per pixel (+ the same again per extra filter pass of a sample).  With a raw
+// uint8 source (mds_aug_raw_t: the reference's frames processor, src/frames.py, folded into a sample's first pass) that pass
+// reads 1 B per source pixel instead of 4; mds_pad_normalize is the same conversion as a stand-alone 1 B in / 4 B out stream.
 #include "elem.h"
 
 // Philox-4x32-10 (Salmon et al., SC'11): counter = element index / 4, key = the job's seed
@@ -47,6 +49,44 @@ MDS_DEV float px(const float* plane, int H, int W, int x, int y) {   // zeros ou
   return in ? v : 0.0f;
 }
 
+// ---- the raw uint8 source (mds_aug_raw_t / mds_pad_normalize): one plane of (sh, sw) bytes placed at (pt, pl) of the H x W frame.
+// The header's conversion is ONE correctly rounded fp32 division - what torch computes for .to(float32) / 255.0; a multiply by
+// 1.0f / 255 rounds 126 of the 256 byte values differently.
+MDS_DEV float u8_unit(unsigned byte) { return (float)byte / 255.0f; }
+struct RawPlane { const unsigned char* p; int sh, sw, pt, pl; float fillv; };
+// frame pixels (gx .. gx + 3, gy), gy inside the frame: converted bytes inside the source rectangle, the converted fill in the
+// pad band, zeros beyond the frame's columns.  Four bytes in one load where the group lies inside the source row at a 4-byte
+// aligned address (source row start, pad_left and src_w decide that), bytes otherwise.
+MDS_DEV f32x4 raw_quad(const RawPlane& s, int W, int gx, int gy) {
+  const int ry = gy - s.pt, rx = gx - s.pl;
+  f32x4 v;
+  if ((unsigned)ry < (unsigned)s.sh) {
+    const unsigned char* p = s.p + (long)ry * s.sw + rx;
+    if (rx >= 0 && rx + 3 < s.sw && ((uintptr_t)p & 3) == 0) {
+      const uint32_t w = *(const uint32_t*)p;
+      return (f32x4){u8_unit(w & 255u), u8_unit((w >> 8) & 255u), u8_unit((w >> 16) & 255u), u8_unit(w >> 24)};
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float e = 0.0f;
+      if ((unsigned)(gx + j) < (unsigned)W) e = (unsigned)(rx + j) < (unsigned)s.sw ? u8_unit(p[j]) : s.fillv;
+      v[j] = e;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (unsigned)(gx + j) < (unsigned)W ? s.fillv : 0.0f;
+  }
+  return v;
+}
+MDS_DEV float raw_px(const RawPlane& s, int H, int W, int x, int y) {   // as px(): zeros outside the frame, clamped address, masked value
+  const bool in = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+  const int rx = x - s.pl, ry = y - s.pt;
+  const bool rect = (unsigned)rx < (unsigned)s.sw && (unsigned)ry < (unsigned)s.sh;
+  const int xc = rx < 0 ? 0 : (rx >= s.sw ? s.sw - 1 : rx), yc = ry < 0 ? 0 : (ry >= s.sh ? s.sh - 1 : ry);
+  const float v = u8_unit(s.p[(long)yc * s.sw + xc]);
+  return in ? (rect ? v : s.fillv) : 0.0f;
+}
+
 __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
   __shared__ float tile[AUG_LDS_FLOATS];
   const int b = blockIdx.z, t = blockIdx.y;
@@ -55,7 +95,12 @@ __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
   const int H = a.H, W = a.W, tiles_x = (W + AUG_TC - 1) / AUG_TC;
   const int ty0 = (int)(blockIdx.x / tiles_x) * AUG_TR, tx0 = (int)(blockIdx.x % tiles_x) * AUG_TC;
   const long plane_off = ((long)b * a.T + t) * H * W;
-  const float* src = a.buf[jb.src] + plane_off;
+  // a job with src 0 reads the raw uint8 batch where the launch has one: converted where it is loaded (staging loop, COPY, the
+  // direct gathers), fp32 from there on
+  const bool raw = a.raw.u8 != nullptr && jb.src == 0;
+  const RawPlane rs = {raw ? a.raw.u8 + ((long)b * a.T + t) * a.raw.src_h * a.raw.src_w : nullptr, a.raw.src_h, a.raw.src_w,
+                       a.raw.pad_top, a.raw.pad_left, u8_unit((unsigned)a.raw.fill)};
+  const float* src = raw ? nullptr : a.buf[jb.src] + plane_off;
   float* dst = a.buf[jb.dst] + plane_off;
   const int mode = jb.mode, tid = threadIdx.x;
   const int y = ty0 + (tid >> 5), x0 = tx0 + 4 * (tid & 31);
@@ -100,7 +145,8 @@ __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
       const int gy = by0 + r, gx = bx0 + c4;
       f32x4 v4 = {0.f, 0.f, 0.f, 0.f};
       if ((unsigned)gy < (unsigned)H) {
-        if (vec && gx >= 0 && gx + 3 < W) v4 = *(const f32x4*)(src + (long)gy * W + gx);
+        if (raw) v4 = raw_quad(rs, W, gx, gy);
+        else if (vec && gx >= 0 && gx + 3 < W) v4 = *(const f32x4*)(src + (long)gy * W + gx);
         else {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v4[j] = (unsigned)(gx + j) < (unsigned)W ? src[(long)gy * W + gx + j] : 0.f;
@@ -116,8 +162,10 @@ __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
       const int lx = gx - bx0, ly = gy - by0;
       return ((unsigned)lx < (unsigned)bw && (unsigned)ly < (unsigned)bh) ? tile[ly * bw + lx] : 0.f;
     }
-    return px(src, H, W, gx, gy);
+    return raw ? raw_px(rs, H, W, gx, gy) : px(src, H, W, gx, gy);
   };
+  f32x4 cq = {0.f, 0.f, 0.f, 0.f};
+  if (raw && mode == MDS_AUG_COPY) cq = raw_quad(rs, W, x0, y);      // COPY of a raw source: the plain pad + normalize
   float v[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -125,7 +173,7 @@ __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
     float r = 0.0f;
     if (x < W) {
       if (mode == MDS_AUG_COPY) {
-        r = src[(long)y * W + x];
+        r = raw ? cq[j] : src[(long)y * W + x];
       } else if (mode == MDS_AUG_WARP) {
         // torch grid_sample(bilinear, zeros, align_corners=True): pixel coordinates, each corner weighted if inside
         const float sx = m[0] * (float)x + m[1] * (float)y + m[2], sy = m[3] * (float)x + m[4] * (float)y + m[5];
@@ -149,7 +197,7 @@ __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
         const float* c0 = tile + (y - by0) * bw + (x - bx0);
         for (int k = 0; k < ntaps; ++k) r += tapw[k] * c0[tapo[k]];
       } else {
-        for (int k = 0; k < jb.ntaps; ++k) r += jb.tap_w[k] * px(src, H, W, x + jb.tap_dx[k], y + jb.tap_dy[k]);
+        for (int k = 0; k < jb.ntaps; ++k) r += jb.tap_w[k] * tap(x + jb.tap_dx[k], y + jb.tap_dy[k]);
       }
     }
     v[j] = r;
@@ -194,12 +242,60 @@ __global__ __launch_bounds__(256) void aug_kernel(mds_aug_args a) {
 }
 
 extern "C" int mds_aug_pass(const mds_aug_args* a, mds_stream_t stream) {
-  MDS_REQUIRE(a && a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->jobs && a->buf[0] && a->buf[1], "aug_pass: bad args");
+  MDS_REQUIRE(a && a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->jobs && (a->buf[0] || a->raw.u8) && a->buf[1], "aug_pass: bad args");
   MDS_REQUIRE((long)a->H * a->W < 2147483647L, "aug_pass: frame too large");
+  if (a->raw.u8) {
+    const mds_aug_raw_t& r = a->raw;
+    MDS_REQUIRE(r.src_h >= 1 && r.src_w >= 1 && r.pad_top >= 0 && r.pad_left >= 0 && (long)r.pad_top + r.src_h <= a->H && (long)r.pad_left + r.src_w <= a->W,
+                "aug_pass: raw source %d x %d at (%d, %d) of a %d x %d frame", r.src_h, r.src_w, r.pad_top, r.pad_left, a->H, a->W);
+    MDS_REQUIRE(r.fill >= 0 && r.fill <= 255, "aug_pass: raw fill = %d (a byte value)", r.fill);
+  }
   const int bx = cdiv(a->H, AUG_TR) * cdiv(a->W, AUG_TC);      // one block per 8 x 128 output tile
   MDS_REQUIRE(a->T <= 65535 && a->B <= 65535, "aug_pass: grid");
   MDS_LAUNCH(aug_kernel, dim3(bx, a->T, a->B), dim3(256), 0, stream, *a);
   return mds_check_launch("aug_pass");
+}
+
+// ------------------------------------------------------------------ the frames processor alone: uint8 planes -> padded fp32 planes
+// HBM streaming: 1 byte read and 4 bytes written per output pixel.  One work item = four consecutive columns of one output row:
+// one 4-byte load (raw_quad) and one 16-byte store per lane, a wave covers 256 contiguous source bytes and 1 KiB of output.
+// grid = (pieces of a plane's H * ceil(W / 4) items, planes), both grid-strided.
+__global__ __launch_bounds__(256) void pad_normalize_kernel(mds_pad_normalize_args a) {
+  const int H = a.H, W = a.W;
+  const unsigned nq = ((unsigned)W + 3u) >> 2, items = (unsigned)H * nq;      // < 2^31: H * W is
+  const float fillv = u8_unit((unsigned)a.fill);
+  const bool vec = (W & 3) == 0 && ((uintptr_t)a.dst & 15) == 0;      // then every row of every plane starts 16-byte aligned
+  for (long n = blockIdx.y; n < a.n; n += gridDim.y) {
+    const RawPlane rs = {a.src + n * a.src_h * a.src_w, a.src_h, a.src_w, a.pad_top, a.pad_left, fillv};
+    float* plane = a.dst + n * H * W;
+    for (unsigned it = blockIdx.x * 256u + threadIdx.x; it < items; it += gridDim.x * 256u) {
+      const unsigned y = it / nq;
+      const int x0 = (int)((it - y * nq) << 2);
+      const f32x4 v = raw_quad(rs, W, x0, (int)y);
+      float* o = plane + (long)y * W + x0;
+      if (vec) *(f32x4*)o = v;
+      else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (x0 + j < W) o[j] = v[j];
+      }
+    }
+  }
+}
+extern "C" long mds_pad_normalize(const mds_pad_normalize_args* a, mds_stream_t stream) {
+  MDS_REQUIRE(a && a->src && a->dst, "pad_normalize: null pointer");
+  MDS_REQUIRE(a->n >= 1 && a->H > 0 && a->W > 0 && (long)a->H * a->W < 2147483647L, "pad_normalize: n = %ld planes of %d x %d", a->n, a->H, a->W);
+  MDS_REQUIRE(a->src_h >= 1 && a->src_w >= 1 && a->pad_top >= 0 && a->pad_left >= 0 && (long)a->pad_top + a->src_h <= a->H && (long)a->pad_left + a->src_w <= a->W,
+              "pad_normalize: source %d x %d at (%d, %d) of a %d x %d frame", a->src_h, a->src_w, a->pad_top, a->pad_left, a->H, a->W);
+  MDS_REQUIRE(a->fill >= 0 && a->fill <= 255, "pad_normalize: fill = %d (a byte value)", a->fill);
+  const long cap = mds_knob(MDS_KNOB_STREAM_BLOCKS) ? mds_knob(MDS_KNOB_STREAM_BLOCKS) : 2048;      // as elem.h::stream_blocks
+  const long items = (long)a->H * ((a->W + 3) / 4);
+  long by = a->n < cap ? a->n : cap;
+  by = by > 65535 ? 65535 : by;
+  long bx = (items + 255) / 256, per = (cap + by - 1) / by;      // about `cap` blocks in all
+  bx = bx > per ? per : bx;
+  MDS_LAUNCH(pad_normalize_kernel, dim3((unsigned)bx, (unsigned)by), dim3(256), 0, stream, *a);
+  return mds_check_launch("pad_normalize");
 }
 
 // ------------------------------------------------------------------ SURVEY 8(f) N4, device side: pitched luma plane -> frames

@@ -12,7 +12,10 @@ Drop-in for ``get_train_augmentations(size)`` of ``src/ball_action/augmentations
   intermediate zero borders; identical to the reference whenever at most one resampling stage fires for a sample;
 * brightness, contrast, posterize and Gaussian noise are applied in the same pass before the only store;
 * sharpness (3x3) and motion blur (11x11 line kernel, built on the host) are spatial filters of the previous stage's output:
-  the samples that drew them (p = 0.2 each) take one extra pass each through a scratch buffer, the others do not.
+  the samples that drew them (p = 0.2 each) take one extra pass each through a scratch buffer, the others do not;
+* with ``frames_processor=`` (an ``mds.frames.PadNormalizeFramesProcessor``) the module takes the RAW (B, T, h, w) uint8 batch:
+  the reference's pad + ``/ 255`` (``src/frames.py``) happens where a sample's first pass loads its source (``mds_aug_raw_t``),
+  and the padded float32 input never exists.
 
 No CPU fallback: CPU tensors raise unless the test-suite's kernel simulator has been injected (``TrainAugmentations._lib``).
 
@@ -31,6 +34,7 @@ import torch
 from torch import nn
 
 from . import cabi
+from .frames import PadNormalizeFramesProcessor
 
 MAX_TAPS = cabi.MDS_AUG_MAX_TAPS
 
@@ -72,8 +76,12 @@ def motion_kernel(ksize: int, angle: float, direction: float) -> np.ndarray:
 class TrainAugmentations(nn.Module):
     """``get_train_augmentations(size)`` with size = (width, height) like the reference's configs (image_size)."""
 
-    def __init__(self, size, seed: Optional[int] = None, compose_geometric: bool = False):
-        """compose_geometric=False (default): the REFERENCE ORDER - each geometric stage resamples the previous stage's output
+    def __init__(self, size, seed: Optional[int] = None, compose_geometric: bool = False, frames_processor=None):
+        """frames_processor: an ``mds.frames.PadNormalizeFramesProcessor`` of the same size - `forward` then also takes the RAW
+        (B, T, h, w) uint8 batch (the fetcher's clips, stacked) and reads it itself: pad + / 255 happen where the first pass
+        loads its source, the padded float32 batch the reference writes (and rewrites three times) never exists.
+
+        compose_geometric=False (default): the REFERENCE ORDER - each geometric stage resamples the previous stage's output
         as kornia's nn.Sequential does (src/ball_action/augmentations.py:10-13); result-identical to the reference for every
         sample (0.46 ms per 4x15x736x1280 batch).  True: the opt-in fast path - camera move, rotation, resized crop and flip
         composed into ONE resampling of the input (0.36 ms; less interpolation blur and no intermediate zero borders than the
@@ -81,6 +89,12 @@ class TrainAugmentations(nn.Module):
         super().__init__()
         self.compose_geometric = bool(compose_geometric)
         self.width, self.height = int(size[0]), int(size[1])
+        if frames_processor is not None:
+            if not isinstance(frames_processor, PadNormalizeFramesProcessor):
+                raise cabi.MdsError("TrainAugmentations: frames_processor is an mds.frames.PadNormalizeFramesProcessor (the pass reads raw frames by its geometry)")
+            if (int(frames_processor.size[0]), int(frames_processor.size[1])) != (self.width, self.height):
+                raise cabi.MdsError(f"TrainAugmentations: the frames processor pads to {tuple(frames_processor.size)}, the augmentations work on {(self.width, self.height)}")
+        self.frames_processor = frames_processor
         r = self.height / self.width                       # `size = size[::-1]; ratio = size[0] / size[1]`
         self.cfg = dict(camera=dict(degrees=(-2.5, 2.5), translate=(0.1, 0.05), scale=(0.95, 1.05), p=0.2),
                         rotation=dict(degrees=(-2.5, 2.5), p=0.3),
@@ -266,12 +280,26 @@ class TrainAugmentations(nn.Module):
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, params: Optional[List[dict]] = None, noise: Optional[torch.Tensor] = None, prepared: Optional[dict] = None):
-        """x: (B, T, H, W) float32 in [0, 1].  `params` (a list of per-sample dicts as `sample_params` returns) and `noise`
-        (standard-normal draws, (B, T, H, W)) are injection points for parity tests; normally both are drawn here.
+        """x: (B, T, H, W) float32 in [0, 1] - or, with a frames processor configured, the raw (B, T, h, w) uint8 batch, which
+        comes back as the augmented (B, T, H, W) float32 batch, bit-identical to forward(frames_processor(x)); a sample no
+        stage fires for is the plain pad + / 255.  Every shape below is the OUTPUT frame's.  `params` (a list of per-sample
+        dicts as `sample_params` returns) and `noise` (standard-normal draws, (B, T, H, W)) are injection points for parity
+        tests; normally both are drawn here.
         `prepared` = the result of `prepare()` for this shape (bench: the launches alone)."""
-        assert x.dim() == 4 and x.dtype == torch.float32, "augmentations take the (B, T, H, W) float32 frame batch"
-        x = x.contiguous()
-        b, t, h, w = x.shape
+        raw = {}          # the launches' `raw` argument: nothing (the fp32 source), or the uint8 batch and where it sits in the frame
+        if torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.uint8:
+            if self.frames_processor is None:
+                raise cabi.MdsError("augmentations: a uint8 batch needs TrainAugmentations(..., frames_processor=...) - without its geometry "
+                                    "the raw frames cannot be placed; there is no eager conversion")
+            if not x.is_contiguous():
+                raise cabi.MdsError("augmentations: the raw uint8 batch must be contiguous (a hidden copy would cost what the fusion saves)")
+            b, t = x.shape[:2]
+            h, w, top, left, fill = self.frames_processor.geometry(x.shape[2], x.shape[3])
+            raw["raw"] = cabi.make("mds_aug_raw_t", u8=x, src_h=x.shape[2], src_w=x.shape[3], pad_top=top, pad_left=left, fill=fill)
+        else:
+            assert x.dim() == 4 and x.dtype == torch.float32, "augmentations take the (B, T, H, W) float32 frame batch"
+            x = x.contiguous()
+            b, t, h, w = x.shape
         lib = self._library(x)
         dev = x.device
         if prepared is None:
@@ -281,13 +309,13 @@ class TrainAugmentations(nn.Module):
             self.last_params = params
         assert prepared["shape"] == (b, t, h, w)
         table, used, jsz = prepared["table"], prepared["used"], prepared["jsz"]
-        out = torch.empty_like(x)
-        bufs = [x.data_ptr(), out.data_ptr(), 0, 0]
+        out = torch.empty(b, t, h, w, dtype=torch.float32, device=dev)
+        bufs = [0 if raw else x.data_ptr(), out.data_ptr(), 0, 0]
         for k in range(prepared["need_scratch"]):
-            key = (k, x.shape, dev)
+            key = (k, out.shape, dev)
             if key not in self._scratch:
-                self._scratch = {kk: v for kk, v in self._scratch.items() if kk[1:] == (x.shape, dev)}
-                self._scratch[key] = torch.empty_like(x)
+                self._scratch = {kk: v for kk, v in self._scratch.items() if kk[1:] == (out.shape, dev)}
+                self._scratch[key] = torch.empty_like(out)
             bufs[2 + k] = self._scratch[key].data_ptr()
         maps_ptr = table.data_ptr() + prepared["nused"] * jsz
         stream = torch.cuda.current_stream(dev).cuda_stream if x.is_cuda else 0
@@ -299,7 +327,7 @@ class TrainAugmentations(nn.Module):
                 if not used[slot]:
                     continue
                 mp = maps_ptr + (slot if slot < self.NWARP else 0) * prepared["map_bytes"]       # each resampling slot has its own maps
-                args = cabi.make("mds_aug_args", B=b, T=t, H=h, W=w, buf=bufs, jobs=table.data_ptr() + k * jsz, maps=mp, noise=noise)
+                args = cabi.make("mds_aug_args", B=b, T=t, H=h, W=w, buf=bufs, jobs=table.data_ptr() + k * jsz, maps=mp, noise=noise, **raw)
                 lib.check(lib.fn["aug_pass"](C.byref(args), stream), "aug_pass")
                 k += 1
         self._last = (table, x, out, noise)      # the launches are asynchronous: their operands outlive this call
@@ -474,7 +502,8 @@ class TimmMixup:
         return x, out.view(target.shape)
 
 
-def get_train_augmentations(size, compose_geometric: bool = False) -> nn.Module:
+def get_train_augmentations(size, compose_geometric: bool = False, frames_processor=None) -> nn.Module:
     """src/ball_action/augmentations.py:7 / src/action/augmentations.py:7.  The default is the reference's stage order
-    (result-identical to it); compose_geometric=True is the opt-in single-resampling form (see TrainAugmentations)."""
-    return TrainAugmentations(size, compose_geometric=compose_geometric)
+    (result-identical to it); compose_geometric=True is the opt-in single-resampling form (see TrainAugmentations).
+    frames_processor: the trainer's mds.frames.PadNormalizeFramesProcessor - the module then takes the raw uint8 batch."""
+    return TrainAugmentations(size, compose_geometric=compose_geometric, frames_processor=frames_processor)

@@ -19,11 +19,16 @@ Backend protocol (what a rocDecode wrapper has to provide):
     seek_and_decode(index) -> Surface   # frame `index`
 Surface = (device_pointer: int, pitch_bytes: int, keepalive: object) of an NV12 (or Y-only) surface whose first `height` rows
 are the luma plane.
+
+``PadNormalizeFramesProcessor`` / ``get_frames_processor`` (below the fetcher) are the drop-ins for ``src/frames.py``: what
+turns the fetcher's uint8 clip into the padded float32 frames the model takes.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
+import math
 from pathlib import Path
 from typing import Any, Optional
 
@@ -138,3 +143,68 @@ class RocDecFrameFetcher:
     def fetch_frames(self, indexes: list[int]) -> torch.Tensor:
         clip = torch.empty(len(indexes), self.height, self.width, dtype=torch.uint8, device=self._device())
         return self.fetch_into(indexes, clip)
+
+
+# ------------------------------------------------------------------------------------------------ frames processor
+class PadNormalizeFramesProcessor:
+    """Drop-in for ``src/frames.py::PadNormalizeFramesProcessor`` (the same constructor and attributes; the reference calls it
+    per sample at ``src/datasets.py:70-73``): the (..., h, w) uint8 luma frames the fetcher delivers -> (..., size[1], size[0])
+    float32, the frames centred in a constant band of ``fill_value`` (top / left pad = the total // 2) and divided by 255 - in
+    ONE launch (``mds_pad_normalize``: bytes read once, floats written once) where the reference runs ``F.pad``,
+    ``.to(float32)`` and ``/ 255.0`` one after the other.  Bit-identical to that torch expression: the kernel's conversion is
+    the same correctly rounded fp32 division.
+
+    Validation and prediction loaders call it as the reference does.  A training loop hands it to
+    ``mds.augment.get_train_augmentations(size, frames_processor=...)`` instead, which then reads the raw clips itself
+    (``geometry()`` is what it takes from here) - the padded float batch is written once, already augmented.
+    No eager fallback: CPU tensors raise unless the test-suite's kernel simulator has been injected (``_lib``)."""
+
+    def __init__(self, size, pad_mode: str = "constant", fill_value: int = 0):
+        self.size = size
+        self.pad_mode = pad_mode
+        self.fill_value = fill_value
+        self._lib = None          # tests inject the kernel simulator here
+        self._last = None
+
+    def geometry(self, height: int, width: int):
+        """(H, W, pad_top, pad_left, fill) of an h x w frame, as pad_to_frames (src/frames.py:12-31) computes them"""
+        if self.pad_mode != "constant":
+            raise NotImplementedError(f"mds.frames: pad_mode '{self.pad_mode}' - the kernels pad with a constant (the reference's configs use nothing else)")
+        fill = int(self.fill_value)
+        if fill != self.fill_value or not 0 <= fill <= 255:
+            raise cabi.MdsError(f"mds.frames: fill_value {self.fill_value!r} - the pad band of uint8 frames holds a byte value, 0 .. 255")
+        height_pad, width_pad = int(self.size[1]) - height, int(self.size[0]) - width
+        assert height_pad >= 0 and width_pad >= 0
+        return int(self.size[1]), int(self.size[0]), height_pad // 2, width_pad // 2, fill
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        if not (torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() >= 2):
+            raise cabi.MdsError("mds.frames: the frames processor takes the fetcher's (..., h, w) uint8 frames; there is no eager path for other types")
+        if not frames.is_contiguous():
+            raise cabi.MdsError("mds.frames: the frames processor takes contiguous frames (a hidden copy would cost more than the launch)")
+        h, w = frames.shape[-2:]
+        H, W, top, left, fill = self.geometry(h, w)
+        if self._lib is None and not frames.is_cuda:
+            raise cabi.MdsError("mds.frames runs on MI355X only: move the frames to cuda")
+        lib = self._lib if self._lib is not None else cabi.load()
+        out = torch.empty(*frames.shape[:-2], H, W, dtype=torch.float32, device=frames.device)
+        n = math.prod(frames.shape[:-2])
+        if n == 0:
+            return out
+        args = cabi.make("mds_pad_normalize_args", src=frames, dst=out, n=n, src_h=h, src_w=w, H=H, W=W, pad_top=top, pad_left=left, fill=fill)
+        stream = torch.cuda.current_stream(frames.device).cuda_stream if frames.is_cuda else 0
+        with torch.cuda.device(frames.device) if frames.is_cuda else contextlib.nullcontext():
+            lib.check(lib.fn["pad_normalize"](C.byref(args), stream), "pad_normalize")
+        self._last = (frames, out)      # the launch is asynchronous: its operands outlive this call
+        return out
+
+
+_FRAME_PROCESSOR_REGISTRY = dict(
+    pad_normalize=PadNormalizeFramesProcessor,
+)
+
+
+def get_frames_processor(name: str, processor_params: dict):
+    """src/frames.py:62"""
+    assert name in _FRAME_PROCESSOR_REGISTRY
+    return _FRAME_PROCESSOR_REGISTRY[name](**processor_params)

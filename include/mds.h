@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 139
+#define MDS_VERSION 140
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -873,7 +873,29 @@ int mds_multi_ema(const mds_ema_args* a, mds_stream_t stream);
  * clamped), contrast (multiplicative, clamped), posterize (bit mask of the 8-bit value), Gaussian noise (from `noise`, or
  * generated in the kernel by Philox-4x32-10 + Box-Muller keyed by the job's seed and the element index).
  * A sample without spatial filters is read once and written once; sharpness / motion blur add one pass each through
- * scratch buffers for the samples that drew them (p = 0.2 each).                                                      */
+ * scratch buffers for the samples that drew them (p = 0.2 each).
+ *
+ * Optional raw source (`raw`, ABI 140; the reference's frames processor src/frames.py:12-54 = F.pad + .to(float32) + / 255.0,
+ * called per sample at src/datasets.py:70-73, folded into the pass): with raw.u8 set, every job whose `src` is 0 reads the
+ * (B, T, src_h, src_w) uint8 batch instead of buf[0], which may then be NULL.  A source pixel (x, y) of such a job is
+ *   inside rows [pad_top, pad_top + src_h) x columns [pad_left, pad_left + src_w):  conv(u8[b][t][y - pad_top][x - pad_left])
+ *   elsewhere inside the H x W frame:                                               conv(fill)
+ *   outside the frame:                                                              0, as for an fp32 source
+ * Conversion (normative): conv(byte) = (float)byte / 255.0f - ONE correctly rounded IEEE fp32 division, which is what torch
+ * computes for `.to(float32) / 255.0`.  A multiply by 1.0f / 255 is a different function (the two differ for 126 of the 256
+ * byte values).  The conversion happens once, where the source is loaded; everything after the load is the fp32 pass, so a
+ * launch from the raw batch equals, bit for bit, the same launch from buf[0] = pad + / 255 of it - and no padded fp32 input
+ * exists.  COPY is then the plain pad + normalize.  Jobs reading scratch (src 2 / 3) are unchanged.  u8 needs no alignment
+ * (four bytes per lane are loaded where a 4-byte group lies inside a source row at a 4-byte aligned address, bytes otherwise).
+ * All-zero `raw` = the fp32 source.
+ * Refused with MDS_ERR_BAD_ARG: buf[0] and raw.u8 both NULL; with raw.u8 set: src_h or src_w < 1, a negative pad,
+ * pad_top + src_h > H, pad_left + src_w > W, fill outside 0 .. 255.                                                   */
+typedef struct {
+  const unsigned char* u8;    /* (B, T, src_h, src_w) contiguous; NULL: jobs with src 0 read buf[0] (fp32) */
+  int src_h, src_w;
+  int pad_top, pad_left;      /* where the source rectangle sits in the H x W frame */
+  int fill;                   /* byte value of the pad band, 0 .. 255 */
+} mds_aug_raw_t;
 #define MDS_AUG_COPY 0
 #define MDS_AUG_WARP 1
 #define MDS_AUG_SHARP 2
@@ -897,12 +919,30 @@ typedef struct {
 } mds_aug_job;
 typedef struct {
   int B, T, H, W;
-  float* buf[4];              /* 0 = input batch (read only), 1 = output batch, 2 / 3 = scratch (only if a job names them) */
+  float* buf[4];              /* 0 = input batch (read only; may be NULL with raw.u8), 1 = output batch, 2 / 3 = scratch (only if a job names them) */
   const mds_aug_job* jobs;    /* device [B] */
   const float* maps;          /* device [B][T][6]: sx = m0 x + m1 y + m2, sy = m3 x + m4 y + m5 (WARP jobs) */
   const float* noise;         /* optional device (B, T, H, W) standard-normal draws; NULL = generate */
+  mds_aug_raw_t raw;          /* optional uint8 source of the jobs with src 0 (all-zero: buf[0]) */
 } mds_aug_args;
 int mds_aug_pass(const mds_aug_args* a, mds_stream_t stream);
+
+/* ---- the reference's frames processor on its own (src/frames.py::PadNormalizeFramesProcessor, pad_mode "constant"): n planes
+ * of (src_h, src_w) uint8 -> n planes of (H, W) fp32, the source rectangle at (pad_top, pad_left), conv(fill) around it, with
+ * the conversion of mds_aug_raw_t (one correctly rounded division by 255.0f).  One streaming launch - the bytes are read once,
+ * the floats written once, 16 bytes per lane where dst is 16-byte aligned and W % 4 == 0; nothing is allocated.  src needs no
+ * alignment, dst 4 bytes.
+ * Refused with MDS_ERR_BAD_ARG: src or dst NULL, n < 1, src_h or src_w < 1, a negative pad, pad_top + src_h > H,
+ * pad_left + src_w > W, H * W >= 2^31, fill outside 0 .. 255.  Returns 0, or a negative MDS_ERR_* code.                 */
+typedef struct {
+  const unsigned char* src;   /* [n][src_h][src_w] */
+  float* dst;                 /* [n][H][W] */
+  long n;
+  int src_h, src_w, H, W;
+  int pad_top, pad_left;
+  int fill;
+} mds_pad_normalize_args;
+long mds_pad_normalize(const mds_pad_normalize_args* a, mds_stream_t stream);
 
 /* ---- Mixup / CutMix of the frame batch, in place (reference src/mixup.py::TimmMixup = timm's Mixup with the batch paired
  * front to back, call site src/argus_models.py:52-53).  Sample i is combined with sample j = B - 1 - i.  One launch covers
