@@ -237,12 +237,8 @@ int conv_fwd_project(const mds_conv_fwd_args* a, mds_stream_t stream) {
   const long total = (long)a->N * gq.tiles_a * gq.tiles_b;
   MDS_REQUIRE(total < 2147483647L, "conv_fwd (project): grid");
   const dim3 grid((unsigned)total), block(256);
-  const bool x3 = MDS_EVAL_X3 && a->dtype == MDS_F32;
-#define CP_GO3(T, IS_, MF_, CF_)                                                                                             \
-  do {                                                                                                                       \
-    if (x3) MDS_LAUNCH((conv_project_kernel<T, IS_, MF_, CF_, (sizeof(T) == 4)>), grid, block, smem, stream, *a, gq);        \
-    else MDS_LAUNCH((conv_project_kernel<T, IS_, MF_, CF_, false>), grid, block, smem, stream, *a, gq);                      \
-  } while (0)
+  // (fp32 in split-bf16 products unless the library is built with -DMDS_EVAL_X3=0: a compile-time choice, one instantiation per type)
+#define CP_GO3(T, IS_, MF_, CF_) MDS_LAUNCH((conv_project_kernel<T, IS_, MF_, CF_, (sizeof(T) == 4 && MDS_EVAL_X3)>), grid, block, smem, stream, *a, gq)
 #define CP_GO2(T, IS_, MF_) do { if (CF == 1) CP_GO3(T, IS_, MF_, 1); else if (CF == 2) CP_GO3(T, IS_, MF_, 2); else CP_GO3(T, IS_, MF_, 3); } while (0)
 #define CP_GO(T)                                                 \
   do {                                                           \

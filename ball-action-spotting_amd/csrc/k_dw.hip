@@ -1,17 +1,18 @@
 // k_dw.hip — depthwise 3x3 (2D, stride 1 / TF-SAME stride 2) and 3x3x3 (3D) convolutions.
 //
 // HBM-bound VALU kernels (9 or 27 MACs per element).  Two generations live here:
-//   * the REGISTER SLIDING-WINDOW kernels (dw2_*, dw2s_*, dw3_*: second half of the file) serve every
-//     layer of the headline configuration: a lane owns a channel pair, a half-wave a 128-byte line, a
-//     thread walks a strip of rows keeping the activated window in registers — no LDS tiles, no
-//     barriers, 3-4 waves per SIMD (2.4-3.4x the tiled kernels);
-//   * the LDS-TILED kernels (dw_fwd_kernel / dw_bwd_kernel, first half) remain for the 3x3x3 case
-//     with T != 5 (frozen-encoder configuration, 11 slices): a block owns an 8x16 pixel patch of a
-//     128-byte channel slab, issues all global loads of the patch (+halo) back to back, applies the
+//   * the LDS-TILED kernels (dw_fwd_kernel / dw_bwd_kernel, the first section) serve only the 3x3x3
+//     case with T != 5 (frozen-encoder configuration, 11 slices): a block owns an 8x16 pixel patch of
+//     a 128-byte channel slab, issues all global loads of the patch (+halo) back to back, applies the
 //     producer's BN+SiLU once per element on the way into LDS (zero padding after the activation) and
-//     walks the T slices with a 3-slot ring.
-// In both, BatchNorm sums and filter gradients are reduced in the block (shuffles / LDS) and written
-// with coalesced atomics in the parameter's own order.
+//     walks the T slices with a 3-slot ring;
+//   * the REGISTER SLIDING-WINDOW kernels (dw2_*, dw2s_*, dw3_*, dw3g_*: the sections after it) serve
+//     every 2D layer and every layer of the headline configuration: a lane owns a channel pair, a
+//     half-wave a 128-byte line, a thread walks a strip of rows keeping the activated window in
+//     registers — no LDS tiles, no barriers, 3-4 waves per SIMD (2.4-3.4x the tiled kernels).
+// The launchers (mds_dw_fwd, mds_dw_bwd) close the file.  In both generations BatchNorm sums and filter
+// gradients are reduced in the block (shuffles / LDS) and written with coalesced atomics in the
+// parameter's own order.
 #include <stdlib.h>
 #include "se_tail.h"
 
@@ -61,14 +62,18 @@ MDS_DEV float sum_same_chunk(float v) {
   return v;
 }
 
-// ------------------------------------------------------------------------------------ forward
-template <typename T, int S, int KT>
+// ------------------------------------------------------------------------------------ 3x3x3, T != 5 (LDS tiles)
+// The two LDS-tiled kernels: 3x3x3, stride 1, pad 1 and nothing else.  They take the 3x3x3 launches whose T is not DW3_T: the
+// fp32 forward, the bf16 forward under MDS_KNOB_DW3G = 1 (otherwise dw3g_fwd_kernel's) and every backward.  Every 2D launch and
+// 3x3x3 at T = 5 go to the sliding-window kernels below.
+// Forward: block = 8x16 OUTPUT pixels of a channel slab; thread = 8 channels x a run of WS pixels of one row.
+template <typename T>
 __global__ __launch_bounds__(256) void dw_fwd_kernel(mds_dw_fwd_args a, int nchunks, int tpb) {
   constexpr int V = 8, CC = DwCfg<T>::CC, NCH = CC / V, NPT = 256 / NCH;
   constexpr int TOH = 8, TOW = 16, WS = TOH * TOW / NPT, NSTR = TOW / WS;
-  constexpr int TH = (TOH - 1) * S + 3, TW = (TOW - 1) * S + 3, NPIX = TH * TW;
+  constexpr int TH = TOH + 2, TW = TOW + 2, NPIX = TH * TW;
   constexpr int MAXL = (NPIX * NCH + 255) / 256;
-  constexpr int NSEG = (WS - 1) * S + 3, NTAP = KT * 9;
+  constexpr int KT = 3, NTAP = KT * 9;             // time taps = slots of the slice ring
   MDS_DYN_SMEM(smem);
   T* tile = (T*)smem;                             // [KT][NPIX][CC]
   float* wl = (float*)(tile + KT * NPIX * CC);    // [NTAP][CC]
@@ -79,7 +84,7 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(mds_dw_fwd_args a, int nchu
   const int cbeg = cz * CC, c0 = cbeg + ch * V;
   const bool cvalid = c0 < C;
   const int oy0 = blockIdx.y * TOH;
-  const int iy0 = oy0 * S - a.pad_t;
+  const int iy0 = oy0 - a.pad_t;
   int ox0 = 0, ix0 = 0;  // set per tile: a block walks `tpb` consecutive tiles along W
   for (int e = tid; e < NTAP * CC; e += 256) {
     const int t = e / CC, c = e - t * CC;
@@ -138,24 +143,24 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(mds_dw_fwd_args a, int nchu
       for (int j = 0; j < V; ++j) acc[o][j] = 0.f;
 #pragma unroll
     for (int dt = 0; dt < KT; ++dt) {
-      const int it = ot + dt - (KT == 3 ? 1 : 0);
+      const int it = ot + dt - 1;
       if (it < 0 || it >= a.T) continue;
-      const T* src = tile + (long)(KT == 3 ? (it % 3) : 0) * NPIX * CC + ch * V;
+      const T* src = tile + (long)(it % KT) * NPIX * CC + ch * V;
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
         float w3[3][V];
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) ldv<V>(wl + ((dt * 3 + ky) * 3 + kx) * CC + ch * V, w3[kx]);
 #pragma unroll
-        for (int s = 0; s < NSEG; ++s) {
+        for (int s = 0; s < WS + 2; ++s) {   // the WS + 2 input columns under this thread's WS outputs
           Raw<T, V> rv;
-          rv.ld(src + (long)((r * S + ky) * TW + sx * WS * S + s) * CC);
+          rv.ld(src + (long)((r + ky) * TW + sx * WS + s) * CC);
           float v[V];
           rv.get(v);
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx) {
-            if ((s - kx) >= 0 && ((s - kx) % S) == 0 && (s - kx) / S < WS) {
-              const int o = (s - kx) / S;
+            if (s - kx >= 0 && s - kx < WS) {
+              const int o = s - kx;
 #pragma unroll
               for (int j = 0; j < V; ++j) acc[o][j] += v[j] * w3[kx][j];
             }
@@ -181,22 +186,13 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(mds_dw_fwd_args a, int nchu
   for (int tt = 0; tt < tpb; ++tt) {
     ox0 = (blockIdx.x * tpb + tt) * TOW;
     if (ox0 >= a.OW) break;
-    ix0 = ox0 * S - a.pad_l;
-    if (KT == 3) {
-      load_slice(0, 0);
-      for (int ot = 0; ot < a.T; ++ot) {
-        if (ot + 1 < a.T) load_slice(ot + 1, (ot + 1) % 3);
-        __syncthreads();
-        compute(ot);
-        __syncthreads();
-      }
-    } else {
-      for (int ot = 0; ot < a.T; ++ot) {
-        load_slice(ot, 0);
-        __syncthreads();
-        compute(ot);
-        __syncthreads();
-      }
+    ix0 = ox0 - a.pad_l;
+    load_slice(0, 0);
+    for (int ot = 0; ot < a.T; ++ot) {
+      if (ot + 1 < a.T) load_slice(ot + 1, (ot + 1) % KT);
+      __syncthreads();
+      compute(ot);
+      __syncthreads();
     }
   }
   if (a.stats) {
@@ -214,6 +210,214 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(mds_dw_fwd_args a, int nchu
         const int slot = (blockIdx.x + blockIdx.y * gridDim.x + n * 5) % MDS_STAT_SLOTS;
         atomicAdd(a.stats + ((long)slot * 2 + k) * C + cbeg + c, st_l[tid]);
       }
+    }
+  }
+}
+
+// Backward: block = 8x16 INPUT pixels of a channel slab; thread = 4 channels x strip(s) of 4 pixels.
+// Produces g = (dgrad) * silu'(z) (gradient wrt the BN output of the producing 1x1 conv), the
+// BN-backward sums of g, and the filter gradient.  dy (+halo) is staged raw in LDS; x needs no
+// halo and stays in registers.
+template <typename T>
+__global__ __launch_bounds__(256) void dw_bwd_kernel(mds_dw_bwd_args a, int nchunks, int tpb) {
+  constexpr int V = 4, CC = DwCfg<T>::CC, NCH = CC / V, NPT = 256 / NCH;
+  constexpr int TIH = 8, TIW = 16, SPT = (TIH * TIW / 4) / NPT;  // strips of 4 pixels per thread
+  constexpr int DTH = TIH + 2, DTW = TIW + 2, DNPIX = DTH * DTW;
+  constexpr int MAXL = (DNPIX * NCH + 255) / 256;
+  constexpr int KT = 3, NTAP = KT * 9;             // time taps = slots of the slice ring
+  MDS_DYN_SMEM(smem);
+  T* dyt = (T*)smem;                             // [KT][DNPIX][CC]
+  float* wl = (float*)(dyt + KT * DNPIX * CC);   // [NTAP][CC]
+  float* dwl = wl + NTAP * CC;                   // [CC][NTAP]
+  double* st_l = (double*)(dwl + NTAP * CC);      // [2][CC] fp64
+  const int tid = threadIdx.x, ch = tid % NCH, pt = tid / NCH;
+  const int C = a.C;
+  const int cz = blockIdx.z % nchunks, n = blockIdx.z / nchunks;
+  const int cbeg = cz * CC, c0 = cbeg + ch * V;
+  const bool cvalid = c0 < C;
+  const int iy0 = blockIdx.y * TIH;
+  const int oy_lo = iy0 - 1;
+  int ix0 = 0, ox_lo = 0;  // set per tile: a block walks `tpb` consecutive tiles along W
+  for (int e = tid; e < NTAP * CC; e += 256) {
+    const int t = e / CC, c = e - t * CC;
+    wl[e] = (cbeg + c < C) ? a.w[(long)(cbeg + c) * NTAP + t] : 0.f;
+    dwl[e] = 0.f;
+  }
+  if (tid < 2 * CC) st_l[tid] = 0.0;
+  float sc[V], sh[V], mu[V], rs[V];
+  if (cvalid) {
+    ldv<V>(a.pro.scale + c0, sc); ldv<V>(a.pro.shift + c0, sh);
+    ldv<V>(a.mean + c0, mu); ldv<V>(a.rstd + c0, rs);
+  }
+  const T* x = (const T*)a.x;
+  const T* dy = (const T*)a.dy;
+  T* g = (T*)a.g;
+  float st[2][V], dwacc[NTAP][V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) { st[0][j] = 0.f; st[1][j] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < NTAP; ++t)
+#pragma unroll
+    for (int j = 0; j < V; ++j) dwacc[t][j] = 0.f;
+
+  auto load_slice = [&](int ot, int slot) {
+    const T* plane = dy + ((long)(n * a.T + ot) * a.OH * a.OW) * C + (cvalid ? c0 : 0);
+    T* dst = dyt + (long)slot * DNPIX * CC + ch * V;
+    Raw<T, V> raw[MAXL];
+#pragma unroll
+    for (int l = 0; l < MAXL; ++l) {
+      const int pix = pt + NPT * l;
+      const int ty = pix / DTW, tx = pix - ty * DTW;
+      if (pix < DNPIX)
+        raw[l].ld(plane + ((long)clampi(oy_lo + ty, 0, a.OH - 1) * a.OW + clampi(ox_lo + tx, 0, a.OW - 1)) * C);
+    }
+#pragma unroll
+    for (int l = 0; l < MAXL; ++l) {
+      const int pix = pt + NPT * l;
+      const int ty = pix / DTW, tx = pix - ty * DTW;
+      if (pix < DNPIX) {
+        const int oy = oy_lo + ty, ox = ox_lo + tx;
+        const bool ok = cvalid && oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW;
+        float v[V];
+        raw[l].get(v);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = ok ? v[j] : 0.f;
+        stv<T, V>(dst + (long)pix * CC, v);
+      }
+    }
+  };
+
+  auto compute = [&](int it, const Raw<T, V> (&xraw)[SPT][4]) {
+#pragma unroll
+    for (int sp = 0; sp < SPT; ++sp) {
+      const int sid = pt + NPT * sp, r = sid / 4, sx = sid % 4;
+      const int iy = iy0 + r, ixb = ix0 + 4 * sx;
+      float xv[4][V], act[4][V], da[4][V];
+#pragma unroll
+      for (int o = 0; o < 4; ++o) {
+        const bool ok = cvalid && iy < a.IH && ixb + o < a.IW;
+        xraw[sp][o].get(xv[o]);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          act[o][j] = ok ? siluf_(xv[o][j] * sc[j] + sh[j]) : 0.f;
+          da[o][j] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int dt = 0; dt < KT; ++dt) {
+        const int ot = it - dt + 1;
+        if (ot < 0 || ot >= a.T) continue;
+        const T* src = dyt + (long)(ot % KT) * DNPIX * CC + ch * V;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          const int oy = iy + a.pad_t - ky;
+          if (oy < 0 || oy >= a.OH) continue;
+          const int trow = oy - oy_lo;
+          float w3[3][V];
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) ldv<V>(wl + ((dt * 3 + ky) * 3 + kx) * CC + ch * V, w3[kx]);
+#pragma unroll
+          for (int s = 0; s < 6; ++s) {
+            // the 6 dy columns ox = ixb - 1 + s under this strip's 4 pixels; tile col = ox - ox_lo
+            const int tcol = 4 * sx + s;
+            Raw<T, V> rv;
+            rv.ld(src + (long)(trow * DTW + tcol) * CC);
+            float v[V];
+            rv.get(v);
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+              for (int o = 0; o < 4; ++o) {
+                if (o - kx + 2 == s) {
+#pragma unroll
+                  for (int j = 0; j < V; ++j) {
+                    da[o][j] += v[j] * w3[kx][j];
+                    dwacc[(dt * 3 + ky) * 3 + kx][j] += v[j] * act[o][j];
+                  }
+                }
+              }
+          }
+        }
+      }
+      if (cvalid && iy < a.IH) {
+        T* grow = g + (((long)(n * a.T + it) * a.IH + iy) * a.IW) * C + c0;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          if (ixb + o < a.IW) {
+            float gv[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+              gv[j] = da[o][j] * silu_gradf_(xv[o][j] * sc[j] + sh[j]);
+              st[0][j] += gv[j];
+              st[1][j] += gv[j] * ((xv[o][j] - mu[j]) * rs[j]);
+            }
+            stv<T, V>(grow + (long)(ixb + o) * C, gv);
+          }
+        }
+      }
+    }
+  };
+
+  auto load_x = [&](int it, Raw<T, V> (&xraw)[SPT][4]) {
+    const T* plane = x + ((long)(n * a.T + it) * a.IH * a.IW) * C + (cvalid ? c0 : 0);
+#pragma unroll
+    for (int sp = 0; sp < SPT; ++sp) {
+      const int sid = pt + NPT * sp, r = sid / 4, sx = sid % 4;
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+        xraw[sp][o].ld(plane + ((long)clampi(iy0 + r, 0, a.IH - 1) * a.IW + clampi(ix0 + 4 * sx + o, 0, a.IW - 1)) * C);
+    }
+  };
+
+  for (int tt = 0; tt < tpb; ++tt) {
+    ix0 = (blockIdx.x * tpb + tt) * TIW;
+    if (ix0 >= a.IW) break;
+    ox_lo = ix0 - 1;
+    load_slice(0, 0);
+    for (int it = 0; it < a.T; ++it) {
+      Raw<T, V> xraw[SPT][4];
+      load_x(it, xraw);
+      if (it + 1 < a.T) load_slice(it + 1, (it + 1) % KT);
+      __syncthreads();
+      compute(it, xraw);
+      __syncthreads();
+    }
+  }
+  // reductions: same-chunk lanes of the wave by shuffles, then LDS, then coalesced global atomics
+  // (deterministic way out: the four waves add to the LDS cells one after the other - four terms per cell, their order counts -
+  //  and the block stores the cells to its slot)
+  const bool det = a.partial.buf != nullptr;
+  for (int w = 0; w < (det ? 4 : 1); ++w) {
+    if (!det || (tid >> 6) == w) {
+#pragma unroll
+      for (int t = 0; t < NTAP; ++t)
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          float s = sum_same_chunk<NCH>(dwacc[t][j]);
+          if ((tid & 63) < NCH) {
+            if (det) dwl[(ch * V + j) * NTAP + t] += s;
+            else atomicAdd(&dwl[(ch * V + j) * NTAP + t], s);
+          }
+        }
+    }
+    if (det) __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float s = sum_same_chunk<NCH>(st[k][j]);
+      if ((tid & 63) < NCH) atomicAdd(&st_l[k * CC + ch * V + j], (double)s);
+    }
+  __syncthreads();
+  for (int e = tid; e < NTAP * CC; e += 256) {
+    if (cbeg + e / NTAP < C) wg_out(wg_base(a.dw, a.partial, (long)C * NTAP, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * n)) + (long)cbeg * NTAP + e, dwl[e], det);
+  }
+  if (tid < 2 * CC) {
+    const int k = tid / CC, c = tid - k * CC;
+    if (cbeg + c < C) {
+      const int slot = (blockIdx.x + blockIdx.y * gridDim.x + n * 5) % MDS_STAT_SLOTS;
+      atomicAdd(a.stats + ((long)slot * 2 + k) * C + cbeg + c, st_l[tid]);
     }
   }
 }
@@ -1296,6 +1500,11 @@ extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
   MDS_REQUIRE(!a->pool || (a->epi.mode != MDS_EPI_NONE && !a->stats && a->pool_inv > 0.f &&
                            ((a->kt == 1 && a->T == 1) || (a->kt == 3 && a->T == DW3_T))),
               "dw_fwd: pooling needs an output transform, no statistics, pool_inv, and a sliding-window kernel (kt == 1 with T == 1, or kt == 3 with T == %d)", DW3_T);
+  // a sliding-window launch: the arguments are the kernel's template head, POOL closes it (2: squeeze-excite tail, 1: pooling, 0: neither)
+#define DW_FWD_GO(...) \
+  do { if (se) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((__VA_ARGS__, 2>), grid, block, 0, stream, *a, g)); \
+       else if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((__VA_ARGS__, 1>), grid, block, 0, stream, *a, g)); \
+       else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((__VA_ARGS__, 0>), grid, block, 0, stream, *a, g)); } while (0)
   if (a->kt == 1 && a->stride == 1) {
     MDS_REQUIRE(a->pad_t == 1 && a->pad_l == 1 && a->OH == a->IH && a->OW == a->IW, "dw_fwd: stride-1 geometry");
     // one or two images (the frame-by-frame predictor): 6-row bands with the shortest strips are 50-110 blocks - under one wave per
@@ -1307,32 +1516,20 @@ extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
     const int R = small ? 2 : 6;
     DwStrips g = dw_strips(images, a->OH, a->OW, a->C, R, dw2_len(images, a->OH, a->OW, a->C, R));
     dim3 grid = dw_grid(g), block(256);
-    if (se) {
-      if (small) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 2, 2>), grid, block, 0, stream, *a, g));
-      else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 6, 2>), grid, block, 0, stream, *a, g));
-    } else if (a->pool) {
-      if (small) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 2, true>), grid, block, 0, stream, *a, g));
-      else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 6, true>), grid, block, 0, stream, *a, g));
-    } else {
-      if (small) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 2>), grid, block, 0, stream, *a, g));
-      else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2_fwd_kernel<T, 6>), grid, block, 0, stream, *a, g));
-    }
+    if (small) DW_FWD_GO(dw2_fwd_kernel<T, 2);
+    else DW_FWD_GO(dw2_fwd_kernel<T, 6);
     return mds_check_launch("dw_fwd");
   }
   if (a->kt == 1 && a->stride == 2) {
     DwStrips g = dw_strips(a->N * a->T, a->OH, a->OW, a->C, 3);
     dim3 grid = dw_grid(g), block(256);
-    if (se) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, 2>), grid, block, 0, stream, *a, g));
-    else if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, true>), grid, block, 0, stream, *a, g));
-    else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw2s_fwd_kernel<T, false>), grid, block, 0, stream, *a, g));
+    DW_FWD_GO(dw2s_fwd_kernel<T);
     return mds_check_launch("dw_fwd");
   }
   if (a->kt == 3 && a->T == DW3_T) {
     DwStrips g = dw_strips(a->N, a->OH, a->OW, a->C, 1, dw3_len(a->N, a->OH, a->OW, a->C, 20));
     dim3 grid = dw_grid(g), block(256);
-    if (se) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, 2>), grid, block, 0, stream, *a, g));
-    else if (a->pool) MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, true>), grid, block, 0, stream, *a, g));
-    else MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH((dw3_fwd_kernel<T, false>), grid, block, 0, stream, *a, g));
+    DW_FWD_GO(dw3_fwd_kernel<T);
     return mds_check_launch("dw_fwd");
   }
   if (a->kt == 3 && a->stride == 1 && a->dtype == MDS_BF16 && a->epi.mode == MDS_EPI_NONE && !a->pool && mds_knob(MDS_KNOB_DW3G) != 1) {   // any other T: time chunks (fp32 would spill: it keeps the LDS-tiled kernel)
@@ -1345,243 +1542,20 @@ extern "C" int mds_dw_fwd(const mds_dw_fwd_args* a, mds_stream_t stream) {
     MDS_LAUNCH((dw3g_fwd_kernel<bf16_t>), grid, block, 0, stream, *a, g, nct);      // (bf16 only: no fp32 instantiation exists)
     return mds_check_launch("dw_fwd");
   }
+#undef DW_FWD_GO
+  // only 3x3x3 at stride 1 gets here: both strides of kt == 1 returned above, and kt == 3 with stride 2 was refused
   MDS_DISPATCH_DTYPE(a->dtype, T, {
     const int CC = DwCfg<T>::CC;
     const int nchunks = cdiv(a->C, CC);
     const int tiles_x = cdiv(a->OW, 16), tpb = 1;  // forward: parallelism beats amortisation
     dim3 grid(cdiv(tiles_x, tpb), cdiv(a->OH, 8), a->N * nchunks), block(256);
-    const int S = a->stride, TH = 7 * S + 3, TW = 15 * S + 3;
-    const size_t smem = (size_t)a->kt * TH * TW * CC * sizeof(T) + ((size_t)a->kt * 9 * CC + 4 * CC) * sizeof(float);
-    if (a->kt == 3) MDS_LAUNCH((dw_fwd_kernel<T, 1, 3>), grid, block, smem, stream, *a, nchunks, tpb);
-    else if (S == 1) MDS_LAUNCH((dw_fwd_kernel<T, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
-    else MDS_LAUNCH((dw_fwd_kernel<T, 2, 1>), grid, block, smem, stream, *a, nchunks, tpb);
+    const size_t smem = (size_t)3 * 10 * 18 * CC * sizeof(T) + ((size_t)27 * CC + 4 * CC) * sizeof(float);   // ring of 3 slices of 8x16 (+halo) pixels, taps, statistics
+    MDS_LAUNCH((dw_fwd_kernel<T>), grid, block, smem, stream, *a, nchunks, tpb);
   });
   return mds_check_launch("dw_fwd");
 }
 
 // ------------------------------------------------------------------------------------ backward
-// Block = 8x16 INPUT pixels of a channel slab; thread = 4 channels x strip(s) of 4 pixels.
-// Produces g = (dgrad) * silu'(z) (gradient wrt the BN output of the producing 1x1 conv), the
-// BN-backward sums of g, and the filter gradient.  dy (+halo) is staged raw in LDS; x needs no
-// halo and stays in registers.
-template <typename T, int S, int PL, int KT>
-__global__ __launch_bounds__(256) void dw_bwd_kernel(mds_dw_bwd_args a, int nchunks, int tpb) {
-  constexpr int V = 4, CC = DwCfg<T>::CC, NCH = CC / V, NPT = 256 / NCH;
-  constexpr int TIH = 8, TIW = 16, SPT = (TIH * TIW / 4) / NPT;  // strips of 4 pixels per thread
-  constexpr int DTH = (S == 1) ? TIH + 2 : TIH / 2 + 2, DTW = (S == 1) ? TIW + 2 : TIW / 2 + 2, DNPIX = DTH * DTW;
-  constexpr int MAXL = (DNPIX * NCH + 255) / 256;
-  constexpr int NSEG = (S == 1) ? 6 : 4, NTAP = KT * 9;
-  MDS_DYN_SMEM(smem);
-  T* dyt = (T*)smem;                             // [KT][DNPIX][CC]
-  float* wl = (float*)(dyt + KT * DNPIX * CC);   // [NTAP][CC]
-  float* dwl = wl + NTAP * CC;                   // [CC][NTAP]
-  double* st_l = (double*)(dwl + NTAP * CC);      // [2][CC] fp64
-  const int tid = threadIdx.x, ch = tid % NCH, pt = tid / NCH;
-  const int C = a.C;
-  const int cz = blockIdx.z % nchunks, n = blockIdx.z / nchunks;
-  const int cbeg = cz * CC, c0 = cbeg + ch * V;
-  const bool cvalid = c0 < C;
-  const int iy0 = blockIdx.y * TIH;
-  const int oy_lo = iy0 / S - 1;
-  int ix0 = 0, ox_lo = 0;  // set per tile: a block walks `tpb` consecutive tiles along W
-  for (int e = tid; e < NTAP * CC; e += 256) {
-    const int t = e / CC, c = e - t * CC;
-    wl[e] = (cbeg + c < C) ? a.w[(long)(cbeg + c) * NTAP + t] : 0.f;
-    dwl[e] = 0.f;
-  }
-  if (tid < 2 * CC) st_l[tid] = 0.0;
-  float sc[V], sh[V], mu[V], rs[V];
-  if (cvalid) {
-    ldv<V>(a.pro.scale + c0, sc); ldv<V>(a.pro.shift + c0, sh);
-    ldv<V>(a.mean + c0, mu); ldv<V>(a.rstd + c0, rs);
-  }
-  const T* x = (const T*)a.x;
-  const T* dy = (const T*)a.dy;
-  T* g = (T*)a.g;
-  float st[2][V], dwacc[NTAP][V];
-#pragma unroll
-  for (int j = 0; j < V; ++j) { st[0][j] = 0.f; st[1][j] = 0.f; }
-#pragma unroll
-  for (int t = 0; t < NTAP; ++t)
-#pragma unroll
-    for (int j = 0; j < V; ++j) dwacc[t][j] = 0.f;
-
-  auto load_slice = [&](int ot, int slot) {
-    const T* plane = dy + ((long)(n * a.T + ot) * a.OH * a.OW) * C + (cvalid ? c0 : 0);
-    T* dst = dyt + (long)slot * DNPIX * CC + ch * V;
-    Raw<T, V> raw[MAXL];
-#pragma unroll
-    for (int l = 0; l < MAXL; ++l) {
-      const int pix = pt + NPT * l;
-      const int ty = pix / DTW, tx = pix - ty * DTW;
-      if (pix < DNPIX)
-        raw[l].ld(plane + ((long)clampi(oy_lo + ty, 0, a.OH - 1) * a.OW + clampi(ox_lo + tx, 0, a.OW - 1)) * C);
-    }
-#pragma unroll
-    for (int l = 0; l < MAXL; ++l) {
-      const int pix = pt + NPT * l;
-      const int ty = pix / DTW, tx = pix - ty * DTW;
-      if (pix < DNPIX) {
-        const int oy = oy_lo + ty, ox = ox_lo + tx;
-        const bool ok = cvalid && oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW;
-        float v[V];
-        raw[l].get(v);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[j] = ok ? v[j] : 0.f;
-        stv<T, V>(dst + (long)pix * CC, v);
-      }
-    }
-  };
-
-  auto compute = [&](int it, const Raw<T, V> (&xraw)[SPT][4]) {
-#pragma unroll
-    for (int sp = 0; sp < SPT; ++sp) {
-      const int sid = pt + NPT * sp, r = sid / 4, sx = sid % 4;
-      const int iy = iy0 + r, ixb = ix0 + 4 * sx;
-      float xv[4][V], act[4][V], da[4][V];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        const bool ok = cvalid && iy < a.IH && ixb + o < a.IW;
-        xraw[sp][o].get(xv[o]);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          act[o][j] = ok ? siluf_(xv[o][j] * sc[j] + sh[j]) : 0.f;
-          da[o][j] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int dt = 0; dt < KT; ++dt) {
-        const int ot = it - dt + (KT == 3 ? 1 : 0);
-        if (ot < 0 || ot >= a.T) continue;
-        const T* src = dyt + (long)(KT == 3 ? (ot % 3) : 0) * DNPIX * CC + ch * V;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const int num = iy + a.pad_t - ky;
-          const int oy = num / S;
-          if (num < 0 || (num % S) != 0 || oy >= a.OH) continue;
-          const int trow = oy - oy_lo;
-          float w3[3][V];
-#pragma unroll
-          for (int kx = 0; kx < 3; ++kx) ldv<V>(wl + ((dt * 3 + ky) * 3 + kx) * CC + ch * V, w3[kx]);
-#pragma unroll
-          for (int s = 0; s < NSEG; ++s) {
-            // dy column ox = seg_lo + s, seg_lo = ixb + PL - 2 (S=1) | ixb/2 - 1 (S=2); tile col = ox - ox_lo
-            const int tcol = (S == 1) ? (4 * sx + PL - 1 + s) : (2 * sx + s);
-            Raw<T, V> rv;
-            rv.ld(src + (long)(trow * DTW + tcol) * CC);
-            float v[V];
-            rv.get(v);
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-              for (int o = 0; o < 4; ++o) {
-                const bool hit = (S == 1) ? ((o - kx + 2) == s)
-                                          : ((((o + PL - kx) % 2) == 0) && (((o + PL - kx + 2) / 2) == s));
-                if (hit) {
-#pragma unroll
-                  for (int j = 0; j < V; ++j) {
-                    da[o][j] += v[j] * w3[kx][j];
-                    dwacc[(dt * 3 + ky) * 3 + kx][j] += v[j] * act[o][j];
-                  }
-                }
-              }
-          }
-        }
-      }
-      if (cvalid && iy < a.IH) {
-        T* grow = g + (((long)(n * a.T + it) * a.IH + iy) * a.IW) * C + c0;
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-          if (ixb + o < a.IW) {
-            float gv[V];
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-              gv[j] = da[o][j] * silu_gradf_(xv[o][j] * sc[j] + sh[j]);
-              st[0][j] += gv[j];
-              st[1][j] += gv[j] * ((xv[o][j] - mu[j]) * rs[j]);
-            }
-            stv<T, V>(grow + (long)(ixb + o) * C, gv);
-          }
-        }
-      }
-    }
-  };
-
-  auto load_x = [&](int it, Raw<T, V> (&xraw)[SPT][4]) {
-    const T* plane = x + ((long)(n * a.T + it) * a.IH * a.IW) * C + (cvalid ? c0 : 0);
-#pragma unroll
-    for (int sp = 0; sp < SPT; ++sp) {
-      const int sid = pt + NPT * sp, r = sid / 4, sx = sid % 4;
-#pragma unroll
-      for (int o = 0; o < 4; ++o)
-        xraw[sp][o].ld(plane + ((long)clampi(iy0 + r, 0, a.IH - 1) * a.IW + clampi(ix0 + 4 * sx + o, 0, a.IW - 1)) * C);
-    }
-  };
-
-  for (int tt = 0; tt < tpb; ++tt) {
-    ix0 = (blockIdx.x * tpb + tt) * TIW;
-    if (ix0 >= a.IW) break;
-    ox_lo = ix0 / S - 1;
-    if (KT == 3) {
-      load_slice(0, 0);
-      for (int it = 0; it < a.T; ++it) {
-        Raw<T, V> xraw[SPT][4];
-        load_x(it, xraw);
-        if (it + 1 < a.T) load_slice(it + 1, (it + 1) % 3);
-        __syncthreads();
-        compute(it, xraw);
-        __syncthreads();
-      }
-    } else {
-      for (int it = 0; it < a.T; ++it) {
-        Raw<T, V> xraw[SPT][4];
-        load_x(it, xraw);
-        load_slice(it, 0);
-        __syncthreads();
-        compute(it, xraw);
-        __syncthreads();
-      }
-    }
-  }
-  // reductions: same-chunk lanes of the wave by shuffles, then LDS, then coalesced global atomics
-  // (deterministic way out: the four waves add to the LDS cells one after the other - four terms per cell, their order counts -
-  //  and the block stores the cells to its slot)
-  const bool det = a.partial.buf != nullptr;
-  for (int w = 0; w < (det ? 4 : 1); ++w) {
-    if (!det || (tid >> 6) == w) {
-#pragma unroll
-      for (int t = 0; t < NTAP; ++t)
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-          float s = sum_same_chunk<NCH>(dwacc[t][j]);
-          if ((tid & 63) < NCH) {
-            if (det) dwl[(ch * V + j) * NTAP + t] += s;
-            else atomicAdd(&dwl[(ch * V + j) * NTAP + t], s);
-          }
-        }
-    }
-    if (det) __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float s = sum_same_chunk<NCH>(st[k][j]);
-      if ((tid & 63) < NCH) atomicAdd(&st_l[k * CC + ch * V + j], (double)s);
-    }
-  __syncthreads();
-  for (int e = tid; e < NTAP * CC; e += 256) {
-    if (cbeg + e / NTAP < C) wg_out(wg_base(a.dw, a.partial, (long)C * NTAP, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * n)) + (long)cbeg * NTAP + e, dwl[e], det);
-  }
-  if (tid < 2 * CC) {
-    const int k = tid / CC, c = tid - k * CC;
-    if (cbeg + c < C) {
-      const int slot = (blockIdx.x + blockIdx.y * gridDim.x + n * 5) % MDS_STAT_SLOTS;
-      atomicAdd(a.stats + ((long)slot * 2 + k) * C + cbeg + c, st_l[tid]);
-    }
-  }
-}
-
 // launch geometry of mds_dw_bwd: the launcher and the partial-buffer query both come here
 struct DwBwdGeo { int path; DwStrips g; dim3 grid; int nchunks, tpb; long slots; };      // path 0 / 1 / 2: the sliding-window kernels (3x3 stride 1, stride 2, 3x3x3 at T = 5), 3: the tiled one
 static DwBwdGeo dw_bwd_geo(const mds_dw_bwd_args* a) {
@@ -1593,9 +1567,9 @@ static DwBwdGeo dw_bwd_geo(const mds_dw_bwd_args* a) {
     q.path = 3;
     q.nchunks = cdiv(a->C, a->dtype == MDS_BF16 ? DwCfg<bf16_t>::CC : DwCfg<float>::CC);
     const int tiles_x = cdiv(a->IW, 16);
-    // the per-block fixed cost (tap staging, 36-value wave reductions, atomics) is amortised over a
-    // whole row band in 2D (measured: 342 -> 215 us at 46x80x672); 3D blocks already walk T slices
-    q.tpb = a->kt == 3 ? 2 : (tiles_x < 8 ? tiles_x : 8);
+    // the per-block fixed cost (tap staging, 108-value wave reductions, atomics) is amortised over two
+    // tiles only: the blocks already walk T slices
+    q.tpb = 2;
     q.grid = dim3(cdiv(tiles_x, q.tpb), cdiv(a->IH, 8), a->N * q.nchunks);
     q.slots = (long)q.grid.x * q.grid.y * a->N;      // every (tile run, row band, image) flushes all C channels over its chunk blocks
     return q;
@@ -1638,16 +1612,11 @@ extern "C" int mds_dw_bwd(const mds_dw_bwd_args* a, mds_stream_t stream) {
     });
   } else if (q.path == 2) {
     MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(dw3_bwd_kernel<T>, grid, block, 0, stream, *a, g));
-  } else {
+  } else {   // only 3x3x3 (stride 1, pad 1: checked above) with T != DW3_T gets here: dw_bwd_geo gives every kt == 1 launch a path of its own
     MDS_DISPATCH_DTYPE(a->dtype, T, {
       const int CC = DwCfg<T>::CC;
-      const int nchunks = q.nchunks, tpb = q.tpb;
-      const int dnpix = a->stride == 1 ? 10 * 18 : 6 * 10;
-      const size_t smem = (size_t)a->kt * dnpix * CC * sizeof(T) + ((size_t)2 * a->kt * 9 * CC + 4 * CC) * sizeof(float);
-      if (a->kt == 3) MDS_LAUNCH((dw_bwd_kernel<T, 1, 1, 3>), grid, block, smem, stream, *a, nchunks, tpb);
-      else if (a->stride == 1) MDS_LAUNCH((dw_bwd_kernel<T, 1, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
-      else if (a->pad_l == 0) MDS_LAUNCH((dw_bwd_kernel<T, 2, 0, 1>), grid, block, smem, stream, *a, nchunks, tpb);
-      else MDS_LAUNCH((dw_bwd_kernel<T, 2, 1, 1>), grid, block, smem, stream, *a, nchunks, tpb);
+      const size_t smem = (size_t)3 * 10 * 18 * CC * sizeof(T) + ((size_t)2 * 27 * CC + 4 * CC) * sizeof(float);   // ring of 3 dy slices of 8x16 (+halo) pixels, taps and their gradients, statistics
+      MDS_LAUNCH((dw_bwd_kernel<T>), grid, block, smem, stream, *a, q.nchunks, q.tpb);
     });
   }
   if (int rc = mds_check_launch("dw_bwd")) return rc;

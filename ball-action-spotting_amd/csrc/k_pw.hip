@@ -538,23 +538,19 @@ extern "C" int mds_pw_fwd_split(long M, int K, int N, int dtype) {
 // ------------------------------------------------------------------------------------ wgrad
 // dw[n][k] += sum_m dy[m][n] * pro(x)[m][k]: the MFMA reduction index is the row m, so both operands
 // are needed "transposed" (8 consecutive m per lane).  The staging pass transposes while writing to
-// LDS: element (channel c, row m) lives at c*LDT + 8*((m>>3) ^ ((c>>3)&7)) + (m&7) — bf16 rows are
-// written as (m, m+1) pairs in one dword, the XOR spreads the 8 channel-chunks of a wave over
-// distinct banks, and every fragment is ONE aligned 16-byte LDS read (was 8 two-byte reads, which
-// made this kernel LDS-issue bound).
+// LDS: element (channel c, row m) lives at c*LDT + 8*((m>>3) ^ ((c>>3)&7)) + (m&7) — the XOR spreads
+// the 8 channel-chunks of a wave over distinct banks, and every fragment is ONE aligned LDS read.
+// This generic kernel is instantiated for fp32 only (MW = 1 row per staged word); bf16 launches take
+// pw_wgrad_tr_kernel below.
 #define WG_ROWS 64  // rows staged per step (2 MFMA k-steps of 32 rows)
 // Output tile = (64*NF output channels) x (16*KF input channels); wave w owns n-fragments
 // {NF*w .. NF*w+NF-1} x all KF k-fragments (see the launcher for the measured choice of NF, KF).
 template <typename T> struct WgCfg;
-template <> struct WgCfg<bf16_t> { static const int MW = 2, LDT = WG_ROWS + 8; };
 template <> struct WgCfg<float> { static const int MW = 1, LDT = WG_ROWS + 4; };
 template <int LDT> MDS_DEV int wg_off(int c, int m) { return c * LDT + 8 * ((m >> 3) ^ ((c >> 3) & 7)) + (m & 7); }
-MDS_DEV void wg_put(bf16_t* base, int off, float v0, float v1) {
-  *(uint32_t*)(base + off) = pack2(v0, v1);
-}
 MDS_DEV void wg_put(float* base, int off, float v0, float) { base[off] = v0; }
 
-template <typename T, int PRO, int NF, int KF>
+template <typename T, int PRO, int NF, int KF>   // T = float is the one instantiation
 __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(mds_pw_wgrad_args a, int rows_per_block) {
   typedef typename Frag<T>::type frag_t;
   constexpr int MW = WgCfg<T>::MW, LDT = WgCfg<T>::LDT;
@@ -918,9 +914,9 @@ extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
   const long rpb = g.rpb;
   dim3 grid(cdiv(a->M, rpb), tiles), block(256);
   if (tr) grid = dim3((unsigned)((cdiv(a->M, rpb) + 7) / 8 * 8 * tiles), 1);
-#define WG_GO(T, PRO) \
-  do { const size_t smem_ = (size_t)(KT + NT) * WgCfg<T>::LDT * sizeof(T); \
-       MDS_LAUNCH((pw_wgrad_kernel<T, PRO, 2, 4>), grid, block, smem_, stream, *a, (int)rpb); } while (0)
+#define WG_GO(PRO) \
+  do { const size_t smem_ = (size_t)(KT + NT) * WgCfg<float>::LDT * sizeof(float); \
+       MDS_LAUNCH((pw_wgrad_kernel<float, PRO, 2, 4>), grid, block, smem_, stream, *a, (int)rpb); } while (0)
 #define WGT_GO(PRO) \
   do { const size_t smem_ = (size_t)WG_ROWS * (KT + 16 + NT + 16) * sizeof(bf16_t); \
        MDS_LAUNCH((pw_wgrad_tr_kernel<PRO, 2, 4>), grid, block, smem_, stream, *a, (int)rpb, mds_knob(MDS_KNOB_WG_DBG)); } while (0)
@@ -937,16 +933,16 @@ extern "C" int mds_pw_wgrad(const mds_pw_wgrad_args* a, mds_stream_t stream) {
     return wg_finish(a->partial, a->dw, (long)a->N * a->K, g.splits, stream);
   }
 #undef WGT_GO
-  MDS_DISPATCH_DTYPE(a->dtype, T, {
-    switch (a->pro.mode) {
-      case MDS_PRO_NONE: WG_GO(T, MDS_PRO_NONE); break;
-      case MDS_PRO_AFFINE: WG_GO(T, MDS_PRO_AFFINE); break;
-      case MDS_PRO_BN_SILU: WG_GO(T, MDS_PRO_BN_SILU); break;
-      case MDS_PRO_BN_SILU_GATE: WG_GO(T, MDS_PRO_BN_SILU_GATE); break;
-      case MDS_PRO_GATE: WG_GO(T, MDS_PRO_GATE); break;
-      default: mds_set_error("pw_wgrad: prologue mode %d", a->pro.mode); return MDS_ERR_BAD_ARG;
-    }
-  });
+  // bf16 returned above: the generic kernel exists for fp32 alone
+  if (a->dtype != MDS_F32) { mds_set_error("unsupported dtype %d", (int)a->dtype); return MDS_ERR_UNSUPPORTED; }
+  switch (a->pro.mode) {
+    case MDS_PRO_NONE: WG_GO(MDS_PRO_NONE); break;
+    case MDS_PRO_AFFINE: WG_GO(MDS_PRO_AFFINE); break;
+    case MDS_PRO_BN_SILU: WG_GO(MDS_PRO_BN_SILU); break;
+    case MDS_PRO_BN_SILU_GATE: WG_GO(MDS_PRO_BN_SILU_GATE); break;
+    case MDS_PRO_GATE: WG_GO(MDS_PRO_GATE); break;
+    default: mds_set_error("pw_wgrad: prologue mode %d", a->pro.mode); return MDS_ERR_BAD_ARG;
+  }
 #undef WG_GO
   if (int rc = mds_check_launch("pw_wgrad")) return rc;
   return wg_finish(a->partial, a->dw, (long)a->N * a->K, g.splits, stream);

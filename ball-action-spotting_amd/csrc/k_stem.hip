@@ -549,8 +549,9 @@ extern "C" int mds_stem_wgrad(const mds_stem_wgrad_args* a, mds_stream_t stream)
     const size_t smem = (size_t)((2 * SW_ROWS + 1) * 9 + SW_ROWS * SW_COLS + 1) * SW_PITCH * sizeof(bf16_t);
     if (dyp) MDS_LAUNCH(stem_wgrad_tiled_kernel<true>, dim3((unsigned)sg.blocks), dim3(256), smem, stream, *a, tiles_a, tiles_b, tpb);
     else MDS_LAUNCH(stem_wgrad_tiled_kernel<false>, dim3((unsigned)sg.blocks), dim3(256), smem, stream, *a, tiles_a, tiles_b, tpb);
-  } else {
-    MDS_DISPATCH_DTYPE(a->dtype, T, MDS_LAUNCH(stem_wgrad_kernel<T>, dim3((unsigned)sg.blocks), dim3(256), 0, stream, *a));
+  } else {   // the gather kernel exists for fp32 alone
+    if (a->dtype != MDS_F32) { mds_set_error("unsupported dtype %d", (int)a->dtype); return MDS_ERR_UNSUPPORTED; }
+    MDS_LAUNCH(stem_wgrad_kernel<float>, dim3((unsigned)sg.blocks), dim3(256), 0, stream, *a);
   }
   if (int rc = mds_check_launch("stem_wgrad")) return rc;
   return wg_finish(a->partial, a->dw, (long)a->Cout * 27, sg.slots, stream);

@@ -32,8 +32,8 @@
  *        added), before the store rounds them to the storage type - not the stored y.  Their operands are the stored x (and
  *        packed w) through the prologue; the bf16 GEMM / convolution kernels round the activated operand to bf16 once
  *        (after the gate, where there is one).  The depthwise kernels keep the activation in fp32 registers, un-rounded -
- *        except the LDS-tiled bf16 forward (dw_fwd_kernel, reached by bf16 launches only under MDS_KNOB_DW3G = 1), whose
- *        tile holds it in the storage type.
+ *        except the LDS-tiled bf16 forward (dw_fwd_kernel<bf16_t>: 3x3x3 at T != 5, and for bf16 launches only under
+ *        MDS_KNOB_DW3G = 1), whose tile holds it in the storage type.
  *      - `post.stats` (mds_poststat_t): the STORED values - g = the bf16 / fp32 number written to y (x the DropPath factor),
  *        what every later reader of u will read - and xhat = (post.y - mean) * rstd from the fp32 table.
  *      - `stats` of mds_dw_bwd: the fp32 register value gv = (sum dy * w) * silu'(z), before g is stored; xhat from the

@@ -40,7 +40,11 @@ DW_CASES = [  # N,T,H,W,C,stride,kt
     (1, 9, 7, 8, 136, 1, 3),      # 4 / 4 / 1
     (3, 2, 5, 6, 16, 1, 3),
     (2, 1, 23, 37, 72, 1, 1),     # two images, ragged last strip, several strips per block at once
+    # the LDS-tiled kernels (3x3x3, T != 5) past one 8 x 16 tile:
+    (1, 3, 9, 37, 24, 1, 3),      # three column tiles (the backward walks two per block: grid.x = 2, the second block's walk ends early), two row bands - the second ragged -, a partly filled channel slab
+    (2, 1, 5, 7, 24, 1, 3),       # T = 1: a slice ring without a prefetch, both time neighbours out of range
 ]
+DW_TILED_WIDE = DW_CASES[-2]
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -91,7 +95,7 @@ def _dw_fwd_bwd(be, dt, N, T, H, W, C, stride, kt, act_rounded=False):
     the activation silu(x * scale + shift) stays in fp32 registers - it is NOT rounded to the storage type on its way into the
     products - and the forward statistics, the weight gradient and sum g / sum g * xhat are taken of the fp32 register values
     (acc before the store, gv before the store).  The reference is fed the same: x rounded to the storage type, the fp32 tables
-    the kernel is handed, an un-rounded activation.  The one exception is the LDS-tiled bf16 FORWARD dw_fwd_kernel<bf16_t, S, KT>,
+    the kernel is handed, an un-rounded activation.  The one exception is the LDS-tiled bf16 FORWARD dw_fwd_kernel<bf16_t>,
     which bf16 launches reach only under MDS_KNOB_DW3G = 1: its tile holds the activation in the storage type (act_rounded)."""
     rd = torch.float64
     code, tdt = DT[dt]

@@ -545,14 +545,19 @@ def test_dw_grid_orders(be, dt, order, N, T, H, W, C, stride, kt):
                 assert all(l.gy == nchunks and l.gz == 1 for l in ls), ls
 
 
-@pytest.mark.parametrize("N,T,H,W,C,stride,kt", [(2, 3, 5, 7, 24, 1, 3), (2, 11, 6, 13, 72, 1, 3)])
+@pytest.mark.parametrize("N,T,H,W,C,stride,kt", [(2, 3, 5, 7, 24, 1, 3), (2, 11, 6, 13, 72, 1, 3), test_k_dw_stem.DW_TILED_WIDE])
 def test_dw3_tiled_forward_bf16(be, N, T, H, W, C, stride, kt):
-    """dw_fwd_kernel<bf16_t, 1, 3>: the LDS-tiled 3x3x3 forward, which bf16 launches at T != 5 take only with MDS_KNOB_DW3G = 1
-    (by default they take the time-chunked sliding window dw3g_fwd_kernel)"""
+    """dw_fwd_kernel<bf16_t>: the LDS-tiled 3x3x3 forward, which bf16 launches at T != 5 take only with MDS_KNOB_DW3G = 1
+    (by default they take the time-chunked sliding window dw3g_fwd_kernel).  The last case has three tiles along W: three
+    forward blocks, and two blocks of the tiled backward dw_bwd_kernel, which walks two tiles per block (the second block's walk
+    ends after one)"""
     with knobs(be, {cabi.MDS_KNOB_DW3G: 1}):
         test_k_dw_stem._dw_fwd_bwd(be, "bf16", N, T, H, W, C, stride, kt, act_rounded=True)
         ls = be.launches("_fwd_kernel")
         assert ls is None or (len(ls) == 1 and "dw_fwd_kernel" in ls[0].kernel and "dw3g" not in ls[0].kernel), ls
+        lb = be.launches("dw_bwd_kernel")
+        if ls is not None and W == 37:
+            assert ls[0].gx == 3 and len(lb) == 1 and lb[0].gx == 2, (ls, lb)
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
