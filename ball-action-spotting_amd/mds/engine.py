@@ -260,7 +260,13 @@ class Plan:
         self.generation = 0      # bumped by every grad-enabled forward: a stale autograd node must not run
         self.profile = None      # list -> run() brackets every launch with HIP events
         self._lazy: List[Lazy] = []
-        self._zf, self._zb = 0, 0
+        # created on first use
+        self._split_part = self._split_ticket = None       # _split: split-K partial buffer and tickets
+        self._se_ticket = None                             # _se_tickets
+        self._ext = None                                   # _ext_events: kernel stop events
+        self._side = None                                  # _side_stream: the weight-gradient stream, ...
+        self._side_events, self._side_flags = [], {}       # ... its recorded events and, per segment, which launches go there
+        self._x_ref = None                                 # bind_input: keeps the bound frame tensor alive
         self.segs: Dict[str, list] = {"pack": [], "f2d": [], "f3d": [], "fhead": [], "bhead": [], "b3d": [], "b2d": []}
         self._recs: Dict[str, list] = {"2d": [], "3d": [], "head": []}
         self.pack_jobs = []
@@ -271,8 +277,6 @@ class Plan:
         self.masks = []          # (Lazy view, keep_prob)
         self._mask_total = 0
         self.mask_arena = Lazy("own", 0, torch.float32)
-        self.zf_arena = Lazy("own", 0, torch.float32)
-        self.zb_arena = Lazy("own", 0, torch.float32)
         self.zb64_arena = Lazy("own", 0, torch.float64)     # backward BatchNorm sums (fp64 slots)
         self.zf64_arena = Lazy("own", 0, torch.float64)     # forward BatchNorm statistics (fp64 slots)
         self._zb64, self._zf64 = 0, 0
@@ -307,7 +311,7 @@ class Plan:
         S = int(self.lib.fn["pw_fwd_split"](int(M), int(K), int(N_), int(self.code)))
         if S <= 1:
             return {}
-        if getattr(self, "_split_part", None) is None:
+        if self._split_part is None:
             self._split_part = self._own(0, torch.float32)
             self._split_ticket = Lazy("own0", 0, torch.int32)
             self._lazy.append(self._split_ticket)
@@ -318,21 +322,11 @@ class Plan:
     def _se_tickets(self, groups):
         """tickets of a depthwise launch with the squeeze-excite tail (mds_se_tail_t.ticket): like the split-K tickets they reset
         themselves, so one zero-initialised buffer serves every block of the plan - launches of one stream"""
-        if getattr(self, "_se_ticket", None) is None:
+        if self._se_ticket is None:
             self._se_ticket = Lazy("own0", 0, torch.int32)
             self._lazy.append(self._se_ticket)
         self._se_ticket.numel = max(self._se_ticket.numel, int(groups))
         return self._se_ticket
-
-    def zero_fwd(self, n):
-        l = self.zf_arena.sub(self._zf, n)
-        self._zf += n
-        return l
-
-    def zero_bwd(self, n):
-        l = self.zb_arena.sub(self._zb, n)
-        self._zb += n
-        return l
 
     def zero_fwd64(self, n):
         l = self.zf64_arena.sub(self._zf64, n)
@@ -906,8 +900,7 @@ class Plan:
         for seg in dict.fromkeys(sg for sg, _ in self._se_pending):
             self.op(seg, "se_fc_bwd_params_table", _struct="mds_se_fc_bwd_table_args", _jobs=[kw for sg, kw in self._se_pending if sg == seg])
         self._se_pending = []
-        self.zf_arena.numel, self.zb_arena.numel, self.mask_arena.numel, self.zb64_arena.numel = self._zf, self._zb, self._mask_total, self._zb64
-        self.zf64_arena.numel = self._zf64
+        self.mask_arena.numel, self.zb64_arena.numel, self.zf64_arena.numel = self._mask_total, self._zb64, self._zf64
         self.mask_arena.tensor = torch.zeros(max(self.mask_arena.numel, 1), dtype=torch.float32, device=dev)
         # everything a pass zeroes lives in ONE buffer per pass (fp64 part first: 8-byte aligned), so that begin_forward /
         # begin_backward are one memset each instead of two / three dependent launches in front of the first kernel
@@ -921,8 +914,8 @@ class Plan:
                 off += pad(size(a))
             return raw
         self._bind_partials()
-        self._zero_fwd = carve(self.zf64_arena, self.zf_arena)
-        self._zero_bwd = carve(self.zb64_arena, self.zb_arena, self.grad_arena)
+        self._zero_fwd = carve(self.zf64_arena)
+        self._zero_bwd = carve(self.zb64_arena, self.grad_arena)
         for l in self._lazy:
             l.tensor = (torch.zeros if l.kind == "own0" else torch.empty)(max(l.numel, 1), dtype=l.dtype, device=dev)
         if self.masks:
@@ -1062,7 +1055,7 @@ class Plan:
     def _failed(self, rc, name):
         """a launch was refused: split-K and squeeze-excite tickets reset themselves only when a launch completes - zero them so
         that the plan's later launches do not start from a stale count - then raise"""
-        for tk in (getattr(self, "_split_ticket", None), getattr(self, "_se_ticket", None)):
+        for tk in (self._split_ticket, self._se_ticket):
             if tk is not None and tk.tensor is not None:
                 tk.tensor.zero_()
         self.lib.check(rc, name.split("@")[0])
@@ -1165,22 +1158,20 @@ class Plan:
     def _ext_events(self):
         if not self.dev.stop_events:
             return None
-        if getattr(self, "_ext", None) is None:
+        if self._ext is None:
             self._ext = Plan._ExtEvents(self.device, self.dev.event_flags)
         return self._ext
 
     def join_backward(self):
         """the gradient arena is complete once the side stream has drained"""
-        if getattr(self, "_side", None) is not None and self.profile is None:
+        if self._side is not None and self.profile is None:
             torch.cuda.current_stream(self.device).wait_stream(self._side)
 
     def _side_stream(self):
         if self.device.type != "cuda" or not self.dev.side_stream:
             return None
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
-            self._side_events = []
-            self._side_flags = {}
         return self._side
 
     def _run_profiled(self, seg):
@@ -1241,7 +1232,7 @@ class Plan:
         """refresh=False (the stream predictor): the caller runs refresh_weights() itself, and only when a parameter changed.
         rng = (seed, stream, draw): the masks come from mds_mask_fill (include/mds.h has the definition of every element) and
         torch's generator is not touched; a mask_override still wins; plans without masks ignore it."""
-        if self.zf_arena.numel or self.zf64_arena.numel:
+        if self.zf64_arena.numel:
             self._memset(self._zero_fwd)
         if self.masks:
             if mask_override is not None:

@@ -1,7 +1,7 @@
 """Drop-in ``MultiDimStacker`` for MI355X.
 
 Same constructor, attributes, methods and ``state_dict`` as the reference class
-(``/root/reference/src/models/multidim_stacker.py:137-243``); ``src/argus_models.py``,
+(``src/models/multidim_stacker.py:137-243``); ``src/argus_models.py``,
 ``src/predictors.py`` and ``src/ema.py`` run on it unchanged.  All arithmetic
 runs in the hand-written gfx950 kernels of ``libmds_hip.so`` (C ABI: include/mds.h) driven by
 ``engine.Plan``; if the library is missing this module raises — there is no eager/CPU fallback.
@@ -12,7 +12,12 @@ the operator ``torch.ops.mds.backward``), so Dynamo / AOTAutograd / Inductor tra
 ``fullgraph=True`` and see one opaque node each way - the hot path already is a static launch schedule, there is nothing for a
 tracing compiler to add.  The operator finds its module through an integer handle (operators take tensors and scalars,
 not modules); BatchNorm's running statistics are updated by the launch as a side effect, as in eager mode.
-``MDS_CUSTOM_OP=0`` selects the former ``torch.autograd.Function`` behind ``torch.compiler.disable`` (a graph break).
+
+One bridge to a plan: ``KINDS`` says, per plan kind, which segments run and which buffers are the input, the output, the incoming
+gradient and the input gradient, in which of the reference's forms; ``_issue_forward`` / ``_issue_backward`` are the only code that
+stages tensors and issues schedules.  The operator's bodies call them, and so does ``_Bridge``, the one ``torch.autograd.Function``:
+``forward_tail``, ``forward_2d`` / ``forward_3d`` / ``forward_head`` under autograd, and ``forward`` itself with ``MDS_CUSTOM_OP=0``
+(behind ``torch.compiler.disable``: a graph break).
 
 ``forward`` and ``forward_2d`` are differentiable in the frame tensor too: with ``x.requires_grad`` the 2D backward chain ends in the
 stem's data-gradient kernel (``mds_stem_dgrad``) and ``x.grad`` comes back in the caller's ``(B,T,H,W)`` shape.  The chain exists only
@@ -26,7 +31,7 @@ import os
 import warnings
 import weakref
 from collections import OrderedDict
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -73,14 +78,14 @@ class _PlanCache:
 
 
 class _Release:
-    """Marks a plan reusable when the autograd graph that references it dies."""
+    """Marks a plan reusable when the autograd graph that references it dies - unless a later forward has taken the plan since."""
 
     def __init__(self, plan):
-        self.plan = plan
+        self.plan, self.generation = plan, plan.generation
 
     def __del__(self):
         plan = getattr(self, "plan", None)      # __del__ may run on a half-built / torn-down object
-        if plan is not None:
+        if plan is not None and plan.generation == self.generation:
             plan.in_flight = False
 
 
@@ -97,129 +102,154 @@ class _Release2:
             pass
 
 
-class _MDSFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, module, plan, *params):
-        ctx.plan, ctx.module = plan, module
-        ctx.token = _Release(plan)
-        ctx.consumed = False
-        ctx.save_for_backward(x)           # version-checked: an in-place edit of x before backward raises
-        plan.in_flight = True
-        plan.generation += 1
-        ctx.generation = plan.generation
-        with plan.device_guard():
-            plan.bind_input(x)
-            plan.begin_forward(module._mask_override, rng=module._draw(plan))
-            plan.run("f2d"); plan.run("f3d"); plan.run("fhead")
-            B = x.shape[0]
-            return plan.logits.tensor.view(B, -1).clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        plan = ctx.plan
-        if ctx.consumed or ctx.generation != plan.generation:
-            raise RuntimeError("mds: the activations of this forward have been released (backward already ran, or the "
-                               "plan was reused by a later forward); a second backward / retain_graph is not supported")
-        (x,) = ctx.saved_tensors            # raises if x was modified in place since forward
-        ctx.consumed = True
-        flat = _run_backward(ctx.module, plan, x, dlogits)
-        grads = []
-        for p in plan.params:
-            if p.requires_grad:
-                off = plan.poff[id(p)]
-                grads.append(flat[off:off + p.numel()].view(p.shape))
-            else:
-                grads.append(None)
-        dx = _input_grad(plan, x)
-        plan.in_flight = False
-        return (dx, None, None, *grads)
+_RELEASED = ("mds: the activations of this forward have been released (backward already ran, or the plan was reused by a "
+             "later forward); a second backward / retain_graph is not supported")
 
 
-class _TailFunction(torch.autograd.Function):
-    """forward_3d -> forward_head as one differentiable call on given 2D features (fine-tuning the temporal
-    tail on cached features; also how the reference-generated `tail_chain` vectors reach the kernels)."""
-
-    @staticmethod
-    def forward(ctx, feats, module, plan, *params):
-        ctx.plan, ctx.token = plan, _Release(plan)
-        plan.in_flight = True
-        plan.generation += 1
-        ctx.generation, ctx.shape = plan.generation, feats.shape
-        b, s, c, h, w = feats.shape
-        with plan.device_guard():
-            plan.feat.tensor.view(b, s, h, w, c).copy_(feats.detach().permute(0, 1, 3, 4, 2))
-            plan.begin_forward(module._mask_override, rng=module._draw(plan))
-            plan.run("f3d"); plan.run("fhead")
-            return plan.logits.tensor.view(b, -1).clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        plan = ctx.plan
-        if ctx.generation != plan.generation or not plan.in_flight:
-            raise RuntimeError("mds: the activations of this forward have been released")
-        b, s, c, h, w = ctx.shape
-        with plan.device_guard():
-            plan.bind_dlogits(dlogits)
-            plan.begin_backward()
-            plan.run("bhead"); plan.run("b3d")
-            plan.join_backward()
-            flat = plan.grad_arena.tensor.clone()
-            dfeats = plan.dfeat.tensor.view(b, s, h, w, c).permute(0, 1, 4, 2, 3).float().contiguous()
-        grads = [flat[plan.poff[id(p)]:plan.poff[id(p)] + p.numel()].view(p.shape) if p.requires_grad else None
-                 for p in plan.tail_params]
-        plan.in_flight = False
-        return (dfeats, None, None, *grads)
+# ------------------------------------------------------------------------------------------------ the boundary of each plan kind
+class _Kind(NamedTuple):
+    """what crosses the boundary between PyTorch and a plan of one kind.  inp / out / gout / dinp name a buffer of the plan and
+    the form the caller sees it in: "frames" - the (b,t,h,w) frame stack, bound in place (its gradient, `dx`, exists only on a
+    plan with input_grad); "flat" - logits / their gradient; "5d" - (b,s,c,h,w) stacks; "4d" - the merged (b,s*c,h,w)."""
+    fwd: Tuple[str, ...]            # forward segments, in issue order
+    bwd: Tuple[str, ...]            # backward segments, in issue order
+    inp: Tuple[str, str]
+    out: Tuple[str, str]
+    gout: Tuple[str, str]           # where the incoming gradient is staged
+    dinp: Tuple[str, str]           # where the input gradient is read
+    params: Tuple[str, ...]         # name prefixes of the parameters this part of the network owns
 
 
-class _SubFunction(torch.autograd.Function):
-    """forward_2d / forward_3d / forward_head called on their own with autograd on (the reference's are ordinary
-    differentiable methods, multidim_stacker.py:210-237): one plan of that kind with its backward schedule; gradients for
-    the input and for the parameters of that part of the network only."""
+KINDS = {
+    "full": _Kind(("f2d", "f3d", "fhead"), ("bhead", "b3d", "b2d"), ("x_in", "frames"), ("logits", "flat"), ("dlogits", "flat"),
+                  ("dx", "frames"), ("",)),
+    "2d": _Kind(("f2d",), ("b2d",), ("x_in", "frames"), ("feat", "5d"), ("dfeat_in", "5d"), ("dx", "frames"),
+                ("conv2d_encoder.", "conv2d_projection.")),
+    "3d": _Kind(("f3d",), ("b3d",), ("feat", "5d"), ("out3d", "4d"), ("uq_in", "4d"), ("dfeat", "5d"),
+                ("conv3d_encoder.", "conv3d_projection.")),
+    "head": _Kind(("fhead",), ("bhead",), ("yq", "4d"), ("logits", "flat"), ("dlogits", "flat"), ("dyq_out", "4d"),
+                  ("global_pool.", "classifier.")),
+    # forward_3d -> forward_head as one call on given 2D features: everything that is not the 2D encoder
+    "tail": _Kind(("f3d", "fhead"), ("bhead", "b3d"), ("feat", "5d"), ("logits", "flat"), ("dlogits", "flat"), ("dfeat", "5d"),
+                  ("conv3d_encoder.", "conv3d_projection.", "global_pool.", "classifier.")),
+}
+
+
+def _rows(plan, buf):
+    """a buffer of the plan as the kernels address it: channels-last rows [b][s][h][w][c]"""
+    return buf.tensor.view(plan.B, plan.T // plan.m.stack_size, plan.h, plan.w, -1)
+
+
+def _rows_from_5d(plan, buf, t):
+    _rows(plan, buf).copy_(t.detach().permute(0, 1, 3, 4, 2))
+
+
+def _5d_from_rows(plan, buf):
+    """(b,s,c,h,w) like the reference, fp32 - always a copy: the plan's buffer is rewritten by the next step"""
+    return _rows(plan, buf).permute(0, 1, 4, 2, 3).float().clone(memory_format=torch.contiguous_format)
+
+
+def _rows_from_4d(plan, buf, t):
+    b, f, h, w = t.shape
+    s = plan.T // plan.m.stack_size
+    _rows_from_5d(plan, buf, t.reshape(b, s, f // s, h, w))
+
+
+def _4d_from_rows(plan, buf):
+    return _5d_from_rows(plan, buf).flatten(1, 2)
+
+
+def _stage(plan, where, t):
+    """hand a caller's tensor (an input, or the gradient of an output) to the plan"""
+    name, form = where
+    if form == "frames":
+        plan.bind_input(t)          # no staging copy: the stem kernels read the caller's tensor
+    elif form == "flat":
+        plan.bind_dlogits(t)
+    else:
+        (_rows_from_5d if form == "5d" else _rows_from_4d)(plan, getattr(plan, name), t)
+
+
+def _read(plan, where):
+    """an output or an input gradient of the plan in the caller's form - a copy, the plan's buffers are rewritten by the next step"""
+    name, form = where
+    if form == "frames":
+        # None for a plan without the stem's data gradient.  Under data parallelism it is the rank's own (each rank
+        # differentiates its own frames): never all-reduced, it is not part of the gradient arena.
+        return plan.dx.tensor.view(plan.B, plan.T, plan.H, plan.W).clone() if plan.input_grad else None
+    if form == "flat":
+        return getattr(plan, name).tensor.view(plan.B, -1).clone()
+    return (_5d_from_rows if form == "5d" else _4d_from_rows)(plan, getattr(plan, name))
+
+
+def _issue_forward(module, plan, kind, inp):
+    """issue the forward schedule of `plan` on `inp`; returns the output of that kind"""
+    k = KINDS[kind]
+    with plan.device_guard():
+        _stage(plan, k.inp, inp)
+        plan.begin_forward(module._mask_override, rng=module._draw(plan))
+        for seg in k.fwd:
+            plan.run(seg)
+        return _read(plan, k.out)
+
+
+def _issue_backward(module, plan, kind, inp, gout):
+    """issue the backward schedule of `plan`; returns the flat gradient buffer (all parameters, parameter order; averaged over
+    ranks under data parallelism) and the gradient of `inp` (None where the plan has none)"""
+    k = KINDS[kind]
+    sync = getattr(module, "_grad_sync", None) if kind == "full" else None       # only the whole network is data parallel
+    bucketed = hasattr(sync, "on_cut")
+    with plan.device_guard():
+        if k.inp[1] == "frames":
+            plan.bind_input(inp)                   # the stem's weight and data gradients read the frames again
+        _stage(plan, k.gout, gout)                 # (buffers of their own, outside the arena begin_backward zeroes)
+        plan.begin_backward()
+        plan.cut_hook = sync.on_cut if bucketed else None     # all-reduce each slice of the arena as soon as it is final
+        for seg in k.bwd:
+            plan.run(seg)
+        plan.cut_hook = None
+        plan.join_backward()
+        if bucketed:
+            world = sync.finish(plan)
+            flat = plan.grad_arena.tensor / world if world > 1 else plan.grad_arena.tensor.clone()
+        else:
+            flat = plan.grad_arena.tensor.clone()  # one launch; the arena is reused next step
+            if sync is not None:
+                sync(flat)                         # one RCCL all-reduce of the flat buffer
+        return flat, _read(plan, k.dinp)
+
+
+def _param_grads(flat, meta):
+    """the flat gradient buffer cut into per-parameter views; None for a frozen parameter.  `meta`: (offset, numel, shape,
+    requires_grad) per parameter - scalars, so an autograd context can keep it while a compiler traces"""
+    return [flat[off:off + n].view(shape) if req else None for off, n, shape, req in meta]
+
+
+class _Bridge(torch.autograd.Function):
+    """the one differentiable call into a plan, for every kind: forward() with MDS_CUSTOM_OP=0, forward_tail, and forward_2d /
+    forward_3d / forward_head under autograd (the reference's are ordinary differentiable methods, multidim_stacker.py:210-237).
+    Gradients for the input and for the parameters handed in - those of that part of the network.  The plan's activations
+    are this forward's while the plan is in flight and no later forward has bumped its generation."""
 
     @staticmethod
     def forward(ctx, inp, module, plan, kind, *params):
-        ctx.plan, ctx.kind, ctx.token, ctx.module = plan, kind, _Release(plan), module
-        ctx.params = params
+        ctx.module, ctx.plan, ctx.kind = module, plan, kind
         plan.in_flight = True
         plan.generation += 1
-        ctx.generation, ctx.shape = plan.generation, inp.shape
-        ctx.save_for_backward(inp)
-        return module._run_sub(plan, kind, inp)
+        ctx.generation, ctx.release = plan.generation, _Release(plan)
+        ctx.meta = [(plan.poff[id(p)], p.numel(), p.shape, p.requires_grad) for p in params]
+        ctx.save_for_backward(inp)          # version-checked: an in-place edit of the input before backward raises
+        return _issue_forward(module, plan, kind, inp)
 
     @staticmethod
-    def backward(ctx, dout):
-        plan, kind = ctx.plan, ctx.kind
+    def backward(ctx, gout):
+        plan = ctx.plan
         if ctx.generation != plan.generation or not plan.in_flight:
-            raise RuntimeError("mds: the activations of this forward have been released")
-        (inp,) = ctx.saved_tensors
-        m = ctx.module
-        dinp = None
-        with plan.device_guard():
-            plan.begin_backward()
-            if kind == "2d":
-                b, t, h, w = ctx.shape
-                s_ = t // m.stack_size
-                plan.bind_input(inp)
-                plan.dfeat_in.tensor.view(b, s_, plan.h, plan.w, m.num_3d_features).copy_(dout.permute(0, 1, 3, 4, 2))
-                plan.run("b2d")
-                dinp = _input_grad(plan, inp)
-            elif kind == "3d":
-                b, t, c, h, w = ctx.shape
-                cq = m.num_features // t
-                plan.uq_in.tensor.view(b, t, h, w, cq).copy_(dout.view(b, t, cq, h, w).permute(0, 1, 3, 4, 2))
-                plan.run("b3d")
-                dinp = plan.dfeat.tensor.view(b, t, h, w, c).permute(0, 1, 4, 2, 3).float().contiguous()
-            else:
-                b, f, h, w = ctx.shape
-                t = m.num_stacks
-                plan.bind_dlogits(dout)
-                plan.run("bhead")
-                dinp = plan.dyq_out.tensor.view(b, t, h, w, f // t).permute(0, 1, 4, 2, 3).reshape(b, f, h, w).float().contiguous()
-            plan.join_backward()
-            flat = plan.grad_arena.tensor.clone()
-        grads = [flat[plan.poff[id(p)]:plan.poff[id(p)] + p.numel()].view(p.shape) if p.requires_grad else None for p in ctx.params]
+            raise RuntimeError(_RELEASED)
+        (inp,) = ctx.saved_tensors          # raises if the input was modified in place since forward
+        flat, dinp = _issue_backward(ctx.module, plan, ctx.kind, inp, gout)
         plan.in_flight = False
-        return (dinp, None, None, None, *grads)
+        return (dinp, None, None, None, *_param_grads(flat, ctx.meta))
 
 
 # ------------------------------------------------------------------------------------------------ registered operators
@@ -259,11 +289,7 @@ def _op_forward(x: torch.Tensor, params: List[torch.Tensor], handle: int, need_g
         live[token] = plan
         plan.in_flight = True
         plan.generation += 1
-    with plan.device_guard():
-        plan.bind_input(x)
-        plan.begin_forward(m._mask_override, rng=m._draw(plan))
-        plan.run("f2d"); plan.run("f3d"); plan.run("fhead")
-        return plan.logits.tensor.view(b, -1).clone(), torch.tensor(token, dtype=torch.int64)
+    return _issue_forward(m, plan, "full", x), torch.tensor(token, dtype=torch.int64)
 
 
 @_op_forward.register_fake
@@ -278,10 +304,8 @@ def _op_backward(dlogits: torch.Tensor, x: torch.Tensor, token: torch.Tensor, ha
     m = _module_of(handle)
     plan = m._live.pop(int(token.item()), None)          # (a CPU scalar: no device synchronisation)
     if plan is None:
-        raise RuntimeError("mds: the activations of this forward have been released (backward already ran, or the "
-                           "plan was reused by a later forward); a second backward / retain_graph is not supported")
-    flat = _run_backward(m, plan, x, dlogits)
-    dx = _input_grad(plan, x) if input_grad else None
+        raise RuntimeError(_RELEASED)
+    flat, dx = _issue_backward(m, plan, "full", x, dlogits)      # (dx only on a plan with input_grad - what the forward was told)
     plan.in_flight = False
     return flat, (dx if dx is not None else x.new_empty((0,)))
 
@@ -312,51 +336,17 @@ def _op_setup_context(ctx, inputs, output):
     tok = output[1]
     if need_grad and type(tok) is torch.Tensor and not torch.compiler.is_compiling():     # (not while tracing: fake tensors have no value)
         ctx._mds_release = _Release2(handle, int(tok))
-    ctx.meta = [(p.numel(), p.shape, p.requires_grad) for p in params]
+    offs = itertools.accumulate([0] + [p.numel() for p in params])       # all parameters in parameter order: Plan.poff
+    ctx.meta = [(off, p.numel(), p.shape, p.requires_grad) for off, p in zip(offs, params)]
 
 
 def _op_backward_formula(ctx, dlogits, dtoken):
     x, token = ctx.saved_tensors
     flat, dx = torch.ops.mds.backward(dlogits.contiguous(), x, token, ctx.handle, ctx.input_grad)
-    grads, off = [], 0
-    for n, shape, req in ctx.meta:
-        grads.append(flat[off:off + n].view(shape) if req else None)
-        off += n
-    return (dx if ctx.input_grad and dx.numel() else None), grads, None, None, None, None
+    return (dx if ctx.input_grad and dx.numel() else None), _param_grads(flat, ctx.meta), None, None, None, None
 
 
 _op_forward.register_autograd(_op_backward_formula, setup_context=_op_setup_context)
-
-
-def _input_grad(plan, x):
-    """the gradient of the frame tensor after the 2D backward chain of `plan` has been issued, in x's (B,T,H,W) shape - a copy: the
-    plan's buffer is rewritten by the next step.  None for a plan without the stem's data gradient.  Under data parallelism it
-    is the rank's own (each rank differentiates its own frames): never all-reduced, it is not part of the gradient arena."""
-    if not plan.input_grad:
-        return None
-    return plan.dx.tensor.view(x.shape).clone()
-
-
-def _run_backward(module, plan, x, dlogits):
-    """issue the backward schedule of `plan`; returns the flat gradient buffer (averaged over ranks under data parallelism)"""
-    sync = getattr(module, "_grad_sync", None)
-    bucketed = hasattr(sync, "on_cut")
-    with plan.device_guard():
-        plan.bind_input(x)
-        plan.bind_dlogits(dlogits)
-        plan.begin_backward()
-        plan.cut_hook = sync.on_cut if bucketed else None     # data parallel: all-reduce each slice as soon as it is final
-        plan.run("bhead"); plan.run("b3d"); plan.run("b2d")
-        plan.cut_hook = None
-        plan.join_backward()
-        if bucketed:
-            world = sync.finish(plan)
-            flat = plan.grad_arena.tensor / world if world > 1 else plan.grad_arena.tensor.clone()
-        else:
-            flat = plan.grad_arena.tensor.clone()  # one launch; the arena is reused next step
-            if sync is not None:
-                sync(flat)                         # data parallel: one RCCL all-reduce of the flat buffer
-    return flat
 
 
 def _load_pretrained_encoder(encoder: nn.Module, model_name: str, in_chans: int):
@@ -566,50 +556,21 @@ class MultiDimStacker(nn.Module):
         b, t, h, w = x.shape
         plan = self._plan(x, "full", b, t, h, w, need_grad, input_grad=input_grad)
         if need_grad:
-            return _MDSFunction.apply(x, self, plan, *plan.params)
-        with plan.device_guard():
-            plan.bind_input(x)
-            plan.begin_forward(self._mask_override, rng=self._draw(plan))
-            plan.run("f2d"); plan.run("f3d"); plan.run("fhead")
-            return plan.logits.tensor.view(b, -1).clone()
+            return _Bridge.apply(x, self, plan, "full", *plan.params)
+        return _issue_forward(self, plan, "full", x)
 
-    SUB_PARAMS = {"2d": ("conv2d_encoder.", "conv2d_projection."), "3d": ("conv3d_encoder.", "conv3d_projection."),
-                  "head": ("global_pool.", "classifier.")}
+    def _params_of(self, kind):
+        """the parameters of that part of the network, in parameter order"""
+        return [p for n, p in self.named_parameters() if n.startswith(KINDS[kind].params)]
 
     def _sub(self, kind, inp, B, T, H, W):
         """one of the three sub-forwards: inference plan under no_grad (src/predictors.py:58-70), differentiable otherwise"""
-        names = self.SUB_PARAMS[kind]
-        params = [p for n, p in self.named_parameters() if n.startswith(names)]
+        params = self._params_of(kind)
         need_grad = torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in params))
         plan = self._plan(inp, kind, B, T, H, W, need_grad, input_grad=kind == "2d" and self._wants_input_grad(inp))
         if need_grad:
-            return _SubFunction.apply(inp, self, plan, kind, *params)
-        return self._run_sub(plan, kind, inp)
-
-    def _run_sub(self, plan, kind, x):
-        with plan.device_guard():
-            if kind == "2d":
-                b, t, h, w = x.shape
-                plan.bind_input(x)
-                plan.begin_forward(self._mask_override, rng=self._draw(plan))
-                plan.run("f2d")
-                f = plan.feat.tensor.view(b, t // self.stack_size, plan.h, plan.w, self.num_3d_features)
-                return f.permute(0, 1, 4, 2, 3).float().contiguous()      # (b, S, 192, h, w) like the reference
-            if kind == "3d":
-                b, t, c, h, w = x.shape
-                plan.feat.tensor.view(b, t, h, w, c).copy_(x.detach().permute(0, 1, 3, 4, 2))
-                plan.begin_forward(self._mask_override, rng=self._draw(plan))
-                plan.run("f3d")
-                cq = self.num_features // t
-                y = plan.out3d.tensor.view(b, t, h, w, cq)
-                return y.permute(0, 1, 4, 2, 3).reshape(b, self.num_features, h, w).float().contiguous()
-            b, f, h, w = x.shape
-            t = self.num_stacks
-            cq = f // t
-            plan.yq.tensor.view(b, t, h, w, cq).copy_(x.detach().view(b, t, cq, h, w).permute(0, 1, 3, 4, 2))
-            plan.begin_forward(self._mask_override, rng=self._draw(plan))
-            plan.run("fhead")
-            return plan.logits.tensor.view(b, -1).clone()
+            return _Bridge.apply(inp, self, plan, kind, *params)
+        return _issue_forward(self, plan, kind, inp)
 
     @torch.compiler.disable
     def forward_2d(self, x):
@@ -630,8 +591,7 @@ class MultiDimStacker(nn.Module):
         b, t, c, h, w = feats.shape
         assert c == self.num_3d_features and t == self.num_stacks
         plan = self._plan(feats, "tail", b, t * self.stack_size, h, w, True)
-        plan.tail_params = [p for n, p in self.named_parameters() if not n.startswith("conv2d_")]
-        return _TailFunction.apply(feats, self, plan, *plan.tail_params)
+        return _Bridge.apply(feats, self, plan, "tail", *self._params_of("tail"))
 
     @torch.compiler.disable
     def forward_head(self, x):

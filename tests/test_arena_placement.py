@@ -1,7 +1,7 @@
 """Arena-style placement: one case per operator, at the smallest shape its own test has, with the buffers that mds/engine.py
 sub-allocates DENSELY sitting at a 4-byte-only address (Backend.arena -> align=4: address = 4 mod 16), guard bands on both sides.
 
-Which pointer fields can be sub-slices (mds/engine.py: Lazy.sub through Plan.grad / Plan.mask / Plan.zero_*, and carve):
+Which pointer fields can be sub-slices (mds/engine.py: Lazy.sub through Plan.grad / Plan.mask / Plan.zero_*64, and carve):
   - Plan.grad(p): grad_arena at Plan.poff[p] - a running sum of numel() over module.parameters(), so any 4-byte offset; e.g.
     global_pool.p (ONE float) precedes classifier.weight and classifier.bias in every training plan:
         mds_pw_wgrad_args.dw, mds_conv_wgrad_args.dw, mds_stem_wgrad_args.dw, mds_dw_bwd_args.dw,
@@ -12,7 +12,6 @@ Which pointer fields can be sub-slices (mds/engine.py: Lazy.sub through Plan.gra
   - Plan.zero_fwd64 / zero_bwd64 (fp64): BatchNorm sums (SLOTS * 2 * C doubles), squeeze-excite pooled / dgate (groups * mid), GeM
     accum (B * S * cq) - C, mid and cq are multiples of 8, so every offset is a multiple of 64 bytes: no fp64 sub-buffer can sit
     at 8 mod 16, and no case here puts one there
-  - Plan.zero_fwd / zero_bwd (fp32): no caller at present
   - BNL.buf.sub (scale | shift | mean | rstd, C floats apart) and the arenas themselves (carve: 256-byte boundaries): 16-byte
     aligned by construction
 The cases run the operator's own test body - same inputs, same reference, same tolerance - inside Backend.arena(names), which

@@ -155,7 +155,7 @@ def test_the_frozen_encoder_plan_binds_the_tail_only():
 
 @pytest.mark.parametrize("kind", ["tail", "2d", "3d", "head"])
 def test_sub_forward_plans_honour_the_switch(kind):
-    """_TailFunction (forward_tail) and _SubFunction (forward_2d / forward_3d / forward_head under autograd): the plan of that kind
+    """forward_tail and forward_2d / forward_3d / forward_head under autograd (the one autograd bridge, every sub kind): the plan of that kind
     is a deterministic one, every gradient launch of its backward schedule is bound, and its gradients match the default plan's"""
     ref, prod = _pair(KW)
     prod.train()

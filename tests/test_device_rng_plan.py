@@ -230,7 +230,7 @@ print("CHILD OK")
 
 
 def test_the_untraced_path_draws_once_per_call(tmp_path):
-    """MDS_CUSTOM_OP=0 (read at import: a child process): _MDSFunction and the no-grad training forward"""
+    """MDS_CUSTOM_OP=0 (read at import: a child process): the autograd bridge and the no-grad training forward"""
     script = tmp_path / "child.py"
     script.write_text(textwrap.dedent(CHILD.format(paths=PATHS)))
     r = subprocess.run([sys.executable, str(script)], env=dict(os.environ, MDS_CUSTOM_OP="0"), capture_output=True, text=True, timeout=900)

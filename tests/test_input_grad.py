@@ -1,4 +1,5 @@
-"""x.grad from forward() / forward_2d(): the stem's data gradient wired through the planner and the three autograd paths, on the
+"""x.grad from forward() / forward_2d(): the stem's data gradient wired through the planner and both ways into autograd (the registered
+operator; the one autograd bridge, for forward() with MDS_CUSTOM_OP=0 and for forward_2d()), on the
 kernel simulator (CPU) and - marked gpu - on the gfx950 library, against the float64 oracle."""
 import copy
 import os
