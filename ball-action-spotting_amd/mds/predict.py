@@ -99,6 +99,7 @@ class StreamPredictor:
         self.encoder_passes = 0          # 2D-encoder passes issued so far (steady state: one per chunk)
         self.lanes_in_use = 1            # lanes of the last predict_stream (what the device gave: see _lane_streams)
         self._pipe = None                # predict_stream: the streams / lane of the step being issued
+        self._track = None               # predict_track: the PredictionTrack the tail passes write their rows into
         self.reset_buffers()
 
     def _size_rings(self):
@@ -392,6 +393,9 @@ class StreamPredictor:
             self._rows(c, ("g", lane, b, tuple(tuple(s_) for s_ in slots)), ptail.feat.tensor, eb, range(n * b * self.S), self.store, eb,
                        [slots[j][s_] * b + bb for j in range(n) for bb in range(b) for s_ in range(self.S)], eb)
             self._replay(c, "tail", lane)
+            if self._track is not None:       # predict_track: the rows go into the track on this stream - no clone, no per-frame result
+                self._track_rows(ptail.probs.tensor.view(n, -1), indexes[0] - self._predict_offset)
+                return [(None, i - self._predict_offset) for i in indexes]
             probs = ptail.probs.tensor.view(n, -1).clone()          # nn.Sigmoid + the TTA mean came out of the head's launch; the plan's buffer is reused by the next pass
             if pipe is not None:
                 pipe["tail_done"] = torch.cuda.Event()
@@ -428,7 +432,7 @@ class StreamPredictor:
             self._grow_rings(lanes * int(chunk))      # (on the caller's stream, before the lanes are ordered behind it)
             for st in self._streams:              # whatever the caller queued so far (weights, earlier predict calls) comes first
                 st.wait_stream(cur)
-            pending, idx, step, last_ring, stack_ev = [], first_index, 0, None, {}
+            pending = []
 
             def finish(item):
                 res, done, outs = item
@@ -439,27 +443,8 @@ class StreamPredictor:
                 return res
 
             try:
-                for fr in _batched(frames, chunk):
-                    fr = [f.to(dev, non_blocking=True) for f in fr]
-                    batch = fr[0][None] if len(fr) == 1 else torch.stack(fr)
-                    ready = torch.cuda.Event()
-                    ready.record(cur)             # the frames are complete on the caller's stream here ...
-                    lane = enc[step % lanes]
-                    lane.wait_event(ready)        # ... and the lane's ring update starts behind that
-                    if last_ring is not None:     # ... and behind the ring updates of all earlier steps (made on other lanes)
-                        lane.wait_event(last_ring)
-                    pipe = self._pipe = dict(enc=lane, tail=lane, lane=step % lanes, ring=None, tail_done=None, outs=[], stack_ev=stack_ev)
-                    try:
-                        res = self.predict_batch(batch, idx)
-                    finally:
-                        self._pipe = None
-                    last_ring = pipe["ring"]
-                    if len(stack_ev) > 64 * chunk + 256:      # events of stacks no window needs any more
-                        for st in list(stack_ev)[:len(stack_ev) // 2]:
-                            del stack_ev[st]
-                    pending.append((res, pipe["tail_done"], pipe["outs"]))
-                    idx += len(fr)
-                    step += 1
+                for item in self._issue_steps(frames, first_index, chunk, lanes, cur):
+                    pending.append(item)
                     while len(pending) > lanes:
                         yield from finish(pending.pop(0))
                 while pending:
@@ -467,6 +452,93 @@ class StreamPredictor:
             finally:
                 for st in self._streams:          # an abandoned generator leaves nothing running behind the caller's back
                     cur.wait_stream(st)
+
+    def _issue_steps(self, frames, first_index, chunk, lanes, cur):
+        """the host loop of predict_stream / predict_track: step j (``chunk`` frames: ring update, encoder pass, tail pass) is issued
+        on lane j % lanes; yields (the step's results, the event behind its tail pass, the tensors it allocated there)"""
+        dev, enc = cur.device, self._streams
+        idx, step, last_ring, stack_ev = first_index, 0, None, {}
+        for fr in _batched(frames, chunk):
+            fr = [f.to(dev, non_blocking=True) for f in fr]
+            batch = fr[0][None] if len(fr) == 1 else torch.stack(fr)
+            ready = torch.cuda.Event()
+            ready.record(cur)             # the frames are complete on the caller's stream here ...
+            lane = enc[step % lanes]
+            lane.wait_event(ready)        # ... and the lane's ring update starts behind that
+            if last_ring is not None:     # ... and behind the ring updates of all earlier steps (made on other lanes)
+                lane.wait_event(last_ring)
+            pipe = self._pipe = dict(enc=lane, tail=lane, lane=step % lanes, ring=None, tail_done=None, outs=[], stack_ev=stack_ev)
+            try:
+                res = self.predict_batch(batch, idx)
+            finally:
+                self._pipe = None
+            last_ring = pipe["ring"]
+            if len(stack_ev) > 64 * chunk + 256:      # events of stacks no window needs any more
+                for st in list(stack_ev)[:len(stack_ev) // 2]:
+                    del stack_ev[st]
+            idx += len(fr)
+            step += 1
+            yield res, pipe["tail_done"], pipe["outs"]
+
+    # ------------------------------------------------------------------ predictions of a whole half, kept on the device
+    def _track_rows(self, probs, predict_index):
+        """a tail pass's (n, C) probabilities -> the track's rows for predict_index .. predict_index + n - 1, on the current stream"""
+        tr, n = self._track, probs.shape[0]
+        if tr.count == 0:
+            tr.first_index = predict_index          # the first predict index with a complete window
+        row = predict_index - tr.first_index
+        assert row == tr.count, f"predict_track: frame {predict_index} follows {tr.count} rows from frame {tr.first_index}"
+        if row + n > tr.capacity:
+            raise cabi.MdsError(f"predict_track: the track holds {tr.capacity} rows (num_frames was too small): it cannot grow while lanes are in flight")
+        tr.data[row:row + n].copy_(probs)
+        tr.count += n
+
+    @torch.no_grad()
+    def predict_track(self, frames, first_index: int = 0, chunk: int = 1, lanes: int = None, num_frames: int = None, track=None):
+        """``predict_stream`` for a caller that wants the whole half's ``raw_predictions`` on the device (``mds.spotting``): the same
+        passes with the same ``chunk`` and ``lanes``, but a tail pass copies its rows of probabilities into a ``PredictionTrack`` on
+        its lane's stream - no clone, no tuple per frame, no event wait on the caller's stream per step; the caller's stream waits
+        for the lanes once, at the end.  Row j of the track is the prediction for ``track.first_index + j``: exactly the non-None
+        results of ``predict_stream`` in order, ``track.first_index`` being the first predict index with a complete window.
+        The capacity is fixed before the first pass: ``num_frames`` (or ``len(frames)``) rows, or the given ``track``'s own."""
+        from .spotting import PredictionTrack
+        dev = next(self.m.parameters()).device
+        if track is None:
+            if num_frames is None:
+                if not hasattr(frames, "__len__"):
+                    raise ValueError("predict_track: num_frames is needed for an iterable without a length (the track cannot grow while lanes are in flight)")
+                num_frames = len(frames)
+            track = PredictionTrack(max(1, int(num_frames)), self.m.classifier.out_features, dev)
+        elif track.data.device != dev or track.num_classes != self.m.classifier.out_features:
+            raise ValueError("predict_track: the track is on another device or has another number of classes")
+        if not lanes:
+            lanes = 4 if chunk <= 4 else (3 if chunk <= 8 else 2)
+        lanes = max(1, min(int(lanes), self.MAX_LANES, self.MAX_IN_FLIGHT // max(1, int(chunk))))
+        self._track = track
+        try:
+            if dev.type != "cuda":                    # no streams to overlap: plain calls that write into the track
+                idx = first_index
+                for fr in _batched(frames, chunk):
+                    self.predict_batch(torch.stack(list(fr)), idx)
+                    idx += len(fr)
+                return track
+            with torch.cuda.device(dev):
+                self._streams = _lane_streams(dev, self.m._library(next(self.m.parameters())), self.MAX_LANES)
+                lanes = min(lanes, len(self._streams))
+                self.lanes_in_use = lanes
+                cur = torch.cuda.current_stream(dev)
+                self._grow_rings(lanes * int(chunk))
+                for st in self._streams:
+                    st.wait_stream(cur)               # the track's zero-fill and whatever else the caller queued come first
+                try:
+                    for _ in self._issue_steps(frames, first_index, chunk, lanes, cur):
+                        pass
+                finally:
+                    for st in self._streams:          # once, at the end: the rows are complete on the caller's stream behind this
+                        cur.wait_stream(st)
+            return track
+        finally:
+            self._track = None
 
 
 _LANE_STREAMS = {}       # device -> dict(streams, verified, tries): the lane streams of predict_stream

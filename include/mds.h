@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 140
+#define MDS_VERSION 141
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -987,6 +987,90 @@ typedef struct {
   float off_value, on_value;
 } mds_mixup_args;
 long mds_mixup(const mds_mixup_args* a, mds_stream_t stream);
+
+/* ---- Spotting: per-frame probabilities -> spotted actions, on the device (reference src/utils.py::post_processing =
+ * scipy.ndimage.gaussian_filter + scipy.signal.find_peaks(height, distance) once per class, driven by
+ * src/{ball_action,action}/annotations.py::raw_predictions_to_actions; the fold / experiment average of
+ * scripts/ball_action/ensemble.py::load_and_blend_predictions).  One call: blend K prediction tracks, smooth every class's
+ * series, find its local maxima, select by height and distance, and write the kept peaks of every class in row order.
+ * Nothing comes back to the host in between; the call allocates nothing, never synchronises and issues two kernels on `stream`.
+ *
+ * Inputs.  K tracks (1 <= K <= MDS_SPOT_MAX_TRACKS); track k is a row-major fp32 (rows[k], C) buffer - the layout of the
+ * reference's raw_predictions - whose row 0 is frame first[k] (track_f64 = 1, BLEND only: the buffers hold doubles, which
+ * (double)p_k[i] below then reads as they are).  The union of the ranges [first[k], first[k] + rows[k]) must be
+ * ONE contiguous range [lo, lo + N) (the reference's assert in load_and_blend_predictions).  MDS_SPOT_SINGLE takes K == 1 and
+ * works on an fp32 series (scripts/ball_action/predict.py); MDS_SPOT_BLEND takes any K, 1 included, and works on a float64
+ * series (ensemble.py).  `weights`: the 2 * radius + 1 doubles of the smoothing kernel, computed by the caller (the library
+ * never evaluates exp); 0 <= radius <= MDS_SPOT_MAX_RADIUS.  `height`, and `distance` >= 1 (already ceil'ed, as find_peaks does).
+ *
+ * Arithmetic (normative).  Every value below is an IEEE double; every product, sum and quotient is rounded to nearest even on
+ * its own, nothing is contracted into a fused multiply-add.  i is a row of [0, N), frame lo + i.
+ *   Blend.      BLEND:  x[i] = (((0.0 + (double)p_0[i]) + (double)p_1[i]) + ...) / (double)K in track order; a track that does
+ *               not cover frame lo + i is skipped, K stays the divisor.     SINGLE:  x[i] = (double)p_0[i].
+ *   Smoothing.  scipy's correlate1d with a symmetric kernel and mode="reflect": with r = radius and w = weights,
+ *                   acc = x[l] * w[r];   for j = r, r - 1, ..., 1:   acc = acc + (x[R(l - j)] + x[R(l + j)]) * w[r - j]
+ *               R reflects about the edges, d c b a | a b c d | d c b a: with m = i mod 2N (in [0, 2N)), R(i) = m for m < N and
+ *               2N - 1 - m otherwise - also for N < r, where an index reflects more than once.
+ *               y[l] = acc in BLEND mode; in SINGLE mode acc is rounded ONCE to fp32 and y[l] is that fp32 number widened.
+ *   Peaks.      scipy's _local_maxima_1d on y: rows left <= right with y[left - 1] < y[left] == ... == y[right] > y[right + 1],
+ *               1 <= left, right <= N - 2, give one peak at row (left + right) / 2 (integer division).  Rows 0 and N - 1 are
+ *               never peaks, a plateau that touches an edge is none.
+ *   Height.     A peak p stays when height <= y[p].
+ *   Distance.   scipy's _select_by_peak_distance with priority y[p]: the peaks are visited from the highest priority to the
+ *               lowest; a visited peak that is still alive is kept and removes every other peak closer than `distance` rows
+ *               (|p - q| < distance).  Where scipy leaves the order among bit-equal priorities to an unstable sort, this
+ *               library defines it: among equal values the LOWER row has priority.
+ *   Output.     The kept peaks of class c in ascending row order: peak_index[c][k] = p (relative to lo), peak_conf[c][k] = y[p],
+ *               peak_count[c] = their number.  If more than `cap` peaks are kept, peak_count[c] still holds the true number and
+ *               only the first `cap` are written.  A caller that allocates cap = MDS_SPOT_MAX_PEAKS(N, distance) never meets
+ *               that: kept peaks lie in [1, N - 2] and are pairwise at least `distance` rows apart.
+ *               smoothed (optional, NULL skips it): y as (N, C) row-major - fp32 in SINGLE mode, fp64 in BLEND mode.
+ * No floating-point atomics: two runs give identical bytes.
+ *
+ * Kernels.  (1) blend + smoothing: grid (ceil(N / MDS_SPOT_TILE), ceil(C / MDS_SPOT_CLASSES)) blocks of MDS_SPOT_THREADS; a
+ * block holds its tile's rows and an r-row halo of x on each side in LDS as doubles and writes y class-major into the
+ * workspace.  (2) one block of MDS_SPOT_THREADS per class: thread t looks for peaks that START (row `left`) in rows
+ * [t * L, (t + 1) * L), L = ceil(N / MDS_SPOT_THREADS); the candidates that pass `height` are compacted in row order; then rounds:
+ * every undecided candidate that has the highest (value, lower row) among the undecided candidates closer than `distance` is
+ * kept and removes those neighbours - the sequential rule's result, in as many rounds as its longest chain of dependent
+ * decisions (at most the number of kept peaks; a staircase of rising peaks closer than `distance` takes one round per peak).
+ *
+ * workspace: MDS_SPOT_WORKSPACE_BYTES(N, C) bytes, 8-byte aligned, no initialisation needed; workspace_bytes is its capacity.
+ * Alignment otherwise: the element size of each buffer.
+ * Refused with MDS_ERR_BAD_ARG, before anything is launched: C < 1, K outside 1 .. MDS_SPOT_MAX_TRACKS, a mode other than the
+ * two, SINGLE with K != 1 or track_f64, a track with rows[k] < 1 (N < 1) or a NULL pointer, N * C >= 2^31, tracks whose union is not
+ * contiguous, radius outside 0 .. MDS_SPOT_MAX_RADIUS, distance < 1, cap < 1, weights / peak_index / peak_conf / peak_count /
+ * workspace NULL, workspace_bytes too small.  Returns 0, or a negative MDS_ERR_* code.                                     */
+#define MDS_SPOT_SINGLE 0
+#define MDS_SPOT_BLEND 1
+#define MDS_SPOT_MAX_TRACKS 16
+#define MDS_SPOT_MAX_RADIUS 64
+#define MDS_SPOT_TILE 128        /* rows of y per block of the smoothing kernel */
+#define MDS_SPOT_CLASSES 8       /* classes per block of the smoothing kernel */
+#define MDS_SPOT_THREADS 256
+#define MDS_SPOT_WS_BYTES 20     /* workspace bytes per (row, class): y (8), candidate rows (4), their state (4) and round flag (4) */
+#define MDS_SPOT_WORKSPACE_BYTES(N, C) ((long)(N) * (long)(C) * MDS_SPOT_WS_BYTES)
+#define MDS_SPOT_MAX_PEAKS(N, distance) ((N) < 3 ? 1 : ((long)(N) - 3) / (long)(distance) + 1)
+typedef struct {
+  int mode;                   /* MDS_SPOT_* */
+  int K, C;
+  const void* track[MDS_SPOT_MAX_TRACKS];    /* (rows[k], C) fp32 - or float64 with track_f64 */
+  int track_f64;              /* 1: the tracks hold doubles (BLEND only: a series that was blended before, ensemble.py's saved file) */
+  long first[MDS_SPOT_MAX_TRACKS];           /* frame index of row 0 of track k */
+  long rows[MDS_SPOT_MAX_TRACKS];
+  const double* weights;      /* [2 * radius + 1] */
+  int radius;
+  int distance;
+  double height;
+  int cap;                    /* entries per class of peak_index / peak_conf */
+  int* peak_index;            /* (C, cap) out */
+  double* peak_conf;          /* (C, cap) out */
+  int* peak_count;            /* (C) out */
+  void* smoothed;             /* optional (N, C) out: fp32 (SINGLE) / fp64 (BLEND) */
+  void* workspace;
+  long workspace_bytes;
+} mds_spot_args;
+long mds_spot(const mds_spot_args* a, mds_stream_t stream);
 
 /* ---- SURVEY 8(f) N1 (predictor glue): row gather / scatter between the predictor's device rings and the plans' buffers -
  * raw frames ring -> the stem's uint8 input, 2D features -> the feature store, the store's five stacks -> the tail's
