@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define MDS_VERSION 141
+#define MDS_VERSION 142
 #define MDS_F32 0
 #define MDS_BF16 1
 #define MDS_STAT_SLOTS 32
@@ -1071,6 +1071,84 @@ typedef struct {
   long workspace_bytes;
 } mds_spot_args;
 long mds_spot(const mds_spot_args* a, mds_stream_t stream);
+
+/* ---- Epoch metrics on the device: per-class average precision and binary accuracy (reference src/metrics.py:
+ * PerClassMetric.update copies every step's prediction and target to the host, AveragePrecision / Accuracy.compute
+ * concatenate the epoch's arrays and call sklearn's average_precision_score(average=None) / accuracy_score per class).
+ * Two entry points: mds_metric_push appends one step's rows to epoch buffers on the device, mds_metric_eval computes every
+ * class of the first N rows.  Both allocate nothing, never synchronise, refuse bad arguments before anything is launched and
+ * use no floating-point atomics: two runs give identical bytes.
+ *
+ * mds_metric_push.  pred: (B, C) contiguous, MDS_F32 or MDS_BF16, widened to fp32 (exact); target: (B, C) fp32.  The rows go
+ * to rows [row, row + B) of dst_pred and dst_target, both (capacity, C) fp32 row-major - what np.concatenate gives the
+ * reference.  The same launch ADDS to status (int[2], integer atomics; the caller clears it at the start of an epoch):
+ *   status[0] += the number of pushed targets that are neither 0.0f nor 1.0f (-0.0f == 0.0f: not counted; a NaN is counted)
+ *   status[1] += the number of pushed scores that are not finite (NaN, +-inf)
+ * One kernel.  Refused with MDS_ERR_BAD_ARG: B < 1, C < 1, B * C >= 2^31, row < 0, row + B > capacity, a NULL pointer, a dtype
+ * other than the two.
+ *
+ * mds_metric_eval.  `what`: a bit set of MDS_METRIC_AP and MDS_METRIC_ACC.  result: 3 * C + 2 doubles,
+ *   result[c]           AP of class c                     (written with MDS_METRIC_AP)
+ *   result[C + c]       accuracy of class c               (written with MDS_METRIC_ACC)
+ *   result[2 * C + c]   (double)P, the positives of c     (written with MDS_METRIC_AP)
+ *   result[3 * C + 0 / 1]   (double)status[0], (double)status[1]   (always)
+ * so that one device-to-host copy carries everything; a part that is not asked for is not written.
+ *
+ * Arithmetic (normative).  For class c and row i of [0, N): s_i = pred[i][c] and t_i = target[i][c], both fp32; every
+ * comparison is an fp32 comparison (false where a NaN takes part); T = MDS_METRIC_TILE.
+ *   Average precision, without a sort.  pos(i) = (t_i == 1.0f); P = the number of positive rows.  For every positive row j,
+ *   over ALL rows i:   n_j = #{i : s_i >= s_j},   tp_j = #{i : pos(i) and s_i >= s_j},   q_j = (double)tp_j / (double)n_j.
+ *   Tile k covers rows [k T, min(N, (k + 1) T)); its sum S_k = ((0.0 + q_a) + q_b) + ... runs over its positive rows in
+ *   ascending row order (0.0 for a tile without one); total = ((0.0 + S_0) + S_1) + ... in tile order;
+ *   AP = P ? total / (double)P : 0.0.   Every operation is an IEEE double operation rounded to nearest even on its own; nothing
+ *   is contracted.  This is sklearn's step-function sum  sum_g (R_g - R_{g-1}) Prec_g  over the distinct thresholds g: every row
+ *   of a tie group has the group's precision tp / n, and the group's recall step is its number of positives over P.  Without a
+ *   positive row sklearn (1.7) warns and returns 0.0; so does this.
+ *   Accuracy.  hit(i) = ((t_i > threshold) == (s_i > threshold)), threshold an fp32 number; acc = (double)hits / (double)N -
+ *   accuracy_score on the reference's boolean arrays, bit for bit.
+ *
+ * Kernels.  (1) grid (ceil(N / T), C), blocks of T threads; thread j loads row k T + j.  A block whose tile holds a positive row
+ * compacts its positive rows in row order (thread r takes over the r-th of them) and walks all row tiles through LDS (per row
+ * the score, and the score again where the row is positive, NaN where not: two broadcast compares per row), counting n_j and
+ * tp_j in 32-bit integers in the waves that hold a positive row; thread 0 adds the tile's q in row order and writes S_k, the
+ * tile's positives and its hits to the workspace.  (2) one block per class adds the tiles' values in tile order.
+ * The work per class is between N^2 / 4 compares (a few positives in every tile) and N^2 (every row positive: 1.3e9 at
+ * N = 36,000); a tile without a positive row skips the walk.
+ *
+ * workspace: MDS_METRIC_WORKSPACE_BYTES(N, C) bytes, 8-byte aligned, no initialisation needed; workspace_bytes is its capacity.
+ * Refused with MDS_ERR_BAD_ARG: N < 1, C < 1, N * C >= 2^31, `what` outside 1 .. 3, a NULL pointer, workspace_bytes too small.
+ * Both return 0, or a negative MDS_ERR_* code.                                                                            */
+#define MDS_METRIC_AP 1
+#define MDS_METRIC_ACC 2
+#define MDS_METRIC_TILE 256
+#define MDS_METRIC_WS_BYTES 16   /* workspace bytes per (tile, class): S_k (8), the tile's positives (4) and hits (4) */
+#define MDS_METRIC_TILES(N) (((long)(N) + MDS_METRIC_TILE - 1) / MDS_METRIC_TILE)
+#define MDS_METRIC_WORKSPACE_BYTES(N, C) (MDS_METRIC_TILES(N) * (long)(C) * MDS_METRIC_WS_BYTES)
+typedef struct {
+  int dtype;                  /* of pred: MDS_F32 / MDS_BF16 */
+  int B, C;
+  const void* pred;           /* (B, C) */
+  const float* target;        /* (B, C) */
+  float* dst_pred;            /* (capacity, C) */
+  float* dst_target;          /* (capacity, C) */
+  long row;                   /* first row written */
+  long capacity;
+  int* status;                /* [2], accumulated */
+} mds_metric_push_args;
+long mds_metric_push(const mds_metric_push_args* a, mds_stream_t stream);
+typedef struct {
+  int what;                   /* MDS_METRIC_AP | MDS_METRIC_ACC */
+  int C;
+  long N;
+  const float* pred;          /* (N, C): the first N rows of the epoch buffer */
+  const float* target;        /* (N, C) */
+  float threshold;            /* accuracy */
+  const int* status;          /* [2], as mds_metric_push left it */
+  double* result;             /* [3 * C + 2] */
+  void* workspace;
+  long workspace_bytes;
+} mds_metric_eval_args;
+long mds_metric_eval(const mds_metric_eval_args* a, mds_stream_t stream);
 
 /* ---- SURVEY 8(f) N1 (predictor glue): row gather / scatter between the predictor's device rings and the plans' buffers -
  * raw frames ring -> the stem's uint8 input, 2D features -> the feature store, the store's five stacks -> the tail's
