@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 from typing import Dict, List, Optional
 
 import torch
@@ -27,11 +28,6 @@ import torch
 from . import cabi, geometry as geo
 from .options import DevSwitches, PlanOptions
 from .cabi import MDS_STAT_SLOTS as SLOTS
-
-PRO_NONE, PRO_AFFINE, PRO_BN_SILU, PRO_BN_GATE, PRO_GATE = 0, 1, 2, 3, 4
-G_PLAIN, G_SILU, G_SE, G_MASK = 0, 1, 2, 3
-POST_NONE, POST_PLAIN, POST_MASK, POST_SILU = 0, 1, 2, 3
-EPI_NONE, EPI_AFFINE, EPI_BN_SILU = 0, 1, 2
 
 
 class Grad:
@@ -41,6 +37,21 @@ class Grad:
 
     def __init__(self, buf, reduced=None):
         self.buf, self.reduced = buf, reduced
+
+
+class Bwd:
+    """One entry of a backward chain (Plan._recs): the closure fn(seg, dout, nxt_head) -> Grad | None, the lowest
+    gradient-arena offset `lo` its launches add into (required: the bucket cuts rely on it) and the BNL.head() of the BatchNorm
+    whose backward opens it, if the producer of `dout` may take that layer's sums in its epilogue."""
+    __slots__ = ("fn", "lo", "head")
+
+    def __init__(self, fn, lo, head=None):
+        if type(lo) is not int or lo < 0:
+            raise TypeError(f"Bwd: lo must be the closure's lowest gradient-arena offset, not {lo!r}")
+        self.fn, self.lo, self.head = fn, lo, head
+
+    def __call__(self, seg, dout, nxt_head):
+        return self.fn(seg, dout, nxt_head)
 
 
 class Lazy:
@@ -90,8 +101,26 @@ class BNL:
     mean = property(lambda s: s.buf.sub(2 * s.C, s.C))
     rstd = property(lambda s: s.buf.sub(3 * s.C, s.C))
 
-    def pro(self, mode=PRO_BN_SILU, gate=None, rpg=0):
+    def pro(self, mode=cabi.MDS_PRO_BN_SILU, gate=None, rpg=0):
         return dict(mode=mode, scale=self.scale, shift=self.shift, gate=gate, rows_per_group=rpg)
+
+    def epi(self, mode=cabi.MDS_EPI_BN_SILU):
+        """output transform of a producer in an inference plan: it stores act(bn(y)) (mds_epi_t)"""
+        return dict(_struct="mds_epi_t", mode=mode, scale=self.scale, shift=self.shift)
+
+    def sink(self, pb):
+        """what the producer of y does for this layer: an inference plan stores silu(bn(y)), every other plan y and its sums"""
+        return dict(stats=None, epi=self.epi()) if pb.eval_epilogues else dict(stats=self.stats)
+
+    # How a backward closure opens: -> (mds_gsrc_t, reduce) for the incoming gradient `dout`.  Where the producer of dout took this
+    # layer's sums in its epilogue (Bwd.head, mds_poststat_t: dout.reduced is self) no reduce launch follows.
+    def g_act(self, dout):               # layer read through BN + SiLU (head mode POST_SILU: the producer then stores g = u * silu'(z))
+        took = dout.reduced is self
+        return gsrc(cabi.MDS_G_PLAIN if took else cabi.MDS_G_SILU, dout.buf), not took
+
+    def g_res(self, dout, mask, rpg):    # block output bn(y) * DropPath mask (+ shortcut) (head mode POST_MASK / POST_PLAIN)
+        g = gsrc(cabi.MDS_G_PLAIN, dout.buf) if mask is None else gsrc(cabi.MDS_G_MASK, dout.buf, mask=mask, rpg=rpg)
+        return g, dout.reduced is not self
 
     def finalize(self, pb, seg):
         m = self.mod
@@ -198,12 +227,38 @@ def gsrc(mode, u, gate=None, dpooled=None, mask=None, rpg=0):
     return dict(_struct="mds_gsrc_t", mode=mode, u=u, gate=gate, dpooled=dpooled, mask=mask, rows_per_group=rpg)
 
 
+NO_PRO = dict(mode=cabi.MDS_PRO_NONE)      # "no prologue": the consumer reads its input as stored (mds_pro_t)
+
+
+def gate_pro(gate, rpg, bn=None):
+    """prologue of a squeeze-excite block's projection: the gate on a materialised activation, or on silu(bn(y)) of the raw y"""
+    if bn is not None:
+        return bn.pro(cabi.MDS_PRO_BN_SILU_GATE, gate, rpg)
+    return dict(mode=cabi.MDS_PRO_GATE, scale=None, shift=None, gate=gate, rows_per_group=rpg)
+
+
+def _taps_kw(taps, stride):
+    """the tap-list fields of mds_conv_fwd_args / mds_conv_wgrad_args from geometry.py's lists (the input stride's field name is a Python keyword)"""
+    dy, dx, wi = taps
+    return {"is": stride, "ntaps": len(dy), "dy": dy, "dx": dx, "wi": wi, "wtaps": 9}
+
+
 def _hip_path():
     with open("/proc/self/maps") as f:
         for line in f:
             if "libamdhip64" in line:
                 return line.split()[-1]
     raise RuntimeError("libamdhip64 is not mapped in this process")
+
+
+@functools.lru_cache(maxsize=None)
+def _hip():
+    """the HIP runtime of this process (torch mapped it), opened on first use, with the three entry points a plan calls itself"""
+    hip = C.CDLL(_hip_path())
+    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+    hip.hipEventCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+    hip.hipStreamWaitEvent.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
+    return hip
 
 
 class Plan:
@@ -261,8 +316,8 @@ class Plan:
         self.profile = None      # list -> run() brackets every launch with HIP events
         self._lazy: List[Lazy] = []
         # created on first use
-        self._split_part = self._split_ticket = None       # _split: split-K partial buffer and tickets
-        self._se_ticket = None                             # _se_tickets
+        self._split_part = self._split_ticket = None       # _split: split-K partial buffer and tickets (_tickets)
+        self._se_ticket = None                             # _tickets: of the depthwise launches with a squeeze-excite tail
         self._ext = None                                   # _ext_events: kernel stop events
         self._side = None                                  # _side_stream: the weight-gradient stream, ...
         self._side_events, self._side_flags = [], {}       # ... its recorded events and, per segment, which launches go there
@@ -313,20 +368,20 @@ class Plan:
             return {}
         if self._split_part is None:
             self._split_part = self._own(0, torch.float32)
-            self._split_ticket = Lazy("own0", 0, torch.int32)
-            self._lazy.append(self._split_ticket)
         self._split_part.numel = max(self._split_part.numel, S * int(M) * int(N_))
-        self._split_ticket.numel = max(self._split_ticket.numel, -(-int(M) // cabi.MDS_PW_SPLIT_TILE_ROWS) * -(-int(N_) // 128) * cabi.MDS_PW_SPLIT_TICKET_STRIDE)
-        return dict(split=S, split_part=self._split_part, split_ticket=self._split_ticket)
+        tiles = -(-int(M) // cabi.MDS_PW_SPLIT_TILE_ROWS) * -(-int(N_) // 128)
+        return dict(split=S, split_part=self._split_part, split_ticket=self._tickets("_split_ticket", tiles * cabi.MDS_PW_SPLIT_TICKET_STRIDE))
 
-    def _se_tickets(self, groups):
-        """tickets of a depthwise launch with the squeeze-excite tail (mds_se_tail_t.ticket): like the split-K tickets they reset
-        themselves, so one zero-initialised buffer serves every block of the plan - launches of one stream"""
-        if self._se_ticket is None:
-            self._se_ticket = Lazy("own0", 0, torch.int32)
-            self._lazy.append(self._se_ticket)
-        self._se_ticket.numel = max(self._se_ticket.numel, int(groups))
-        return self._se_ticket
+    def _tickets(self, attr, n):
+        """the plan's ticket buffer `attr` (_split_ticket: mds_pw_fwd_args.split_ticket, _se_ticket: mds_se_tail_t.ticket), >= n counters.
+        Tickets reset themselves when a launch completes (_failed: or not), so one zeroed buffer serves every launch of the one stream"""
+        tk = getattr(self, attr)
+        if tk is None:
+            tk = Lazy("own0", 0, torch.int32)
+            self._lazy.append(tk)
+            setattr(self, attr, tk)
+        tk.numel = max(tk.numel, int(n))
+        return tk
 
     def zero_fwd64(self, n):
         l = self.zf64_arena.sub(self._zf64, n)
@@ -385,10 +440,7 @@ class Plan:
                 self.yq, self.bnq = self.act(N * h * w, m.num_features // S), None
             self._build_head(B, S, h, w, self.yq, self.bnq)
         if self.kind == "3d":   # separately-called forward_3d returns the activated projection
-            self.out3d = self.act(N * h * w, m.num_features // S)
-            self.op("f3d", "bn_res", dtype=self.code, M=N * h * w, C=m.num_features // S, y=self.yq,
-                    scale=self.bnq.scale, shift=self.bnq.shift, act=1, mask=None, rows_per_group=0,
-                    shortcut=None, out=self.out3d)
+            self.out3d = self._bn_res("f3d", self.bnq, self.yq, act=1)
         if self.need_grad:
             chain = [(rec, bseg) for name, bseg in (("head", "bhead"), ("3d", "b3d"), ("2d", "b2d")) for rec in reversed(self._recs[name])]
             gout = None
@@ -404,20 +456,16 @@ class Plan:
             # has been issued every parameter at or above min(lo of closures 0..i) is final; a cut after ~1.5 M elements
             # lets the all-reduce of that slice of the flat arena start while the rest of the backward still runs.
             self.cuts = {}           # (segment, number of ops issued) -> (lo, hi) slice of the gradient arena
-            hi, lo, executed = self.grad_arena.numel, self.grad_arena.numel, []
-            def flush_se(bseg):     # the deferred squeeze-excite parameter gradients of the closures issued so far: one launch
-                if self._se_pending:
-                    self.op(bseg, "se_fc_bwd_params_table", _struct="mds_se_fc_bwd_table_args", _jobs=[kw for _, kw in self._se_pending])
-                    self._se_pending = []
+            hi = lo = self.grad_arena.numel
             for i, (rec, bseg) in enumerate(chain):
                 nxt = chain[i + 1][0] if i + 1 < len(chain) else None
                 # `head` of the next closure: the BatchNorm whose backward consumes this closure's output directly
-                gout = rec(bseg, gout, getattr(nxt, "head", None) if self.fuse_bn_bwd else None)
+                gout = rec(bseg, gout, nxt.head if (nxt is not None and self.fuse_bn_bwd) else None)
                 last = gout is None or nxt is None
-                lo = min(lo, getattr(rec, "lo", lo))
+                lo = min(lo, rec.lo)
                 cut = len(self.segs[bseg]) and (hi - lo >= self.BUCKET_ELEMS or last) and hi > lo
                 if cut or last or chain[i + 1][1] != bseg:
-                    flush_se(bseg)          # (a bucket is final only with every launch that adds into it issued)
+                    self._flush_se()        # (a bucket is final only with every launch that adds into it issued)
                 if cut:
                     self.cuts[(bseg, len(self.segs[bseg]))] = (lo, hi)
                     hi = lo
@@ -433,84 +481,83 @@ class Plan:
         y = self.act(M, N_)
         w = wt if wt is not None else self.pack(wparam, cabi.MDS_PACK_OI, N_, K, 1)
         # the K-heavy narrow-N launches read their filter in MFMA-fragment order, straight into registers (k_pwk8.hip)
-        wfrag = (self.pack(wparam, cabi.MDS_PACK_FRAG_OI, N_, K, 1)
-                 if wt is None and epi_mode is None and self.lib.fn["pw_fwd_wants_frag"](int(M), int(K), int(N_), int(self.code), 0) else None)
         if epi_mode is not None:
             assert self.eval_epilogues and stats_bn is not None
-            stats_bn.finalize(self, seg)      # eval table
-            self.op(seg, "pw_fwd", dtype=self.code, M=M, K=K, N=N_, x=x, w=w, y=y, pro=pro or dict(mode=0), residual=residual,
-                    stats=None, epi=dict(_struct="mds_epi_t", mode=epi_mode, scale=stats_bn.scale, shift=stats_bn.shift), **self._split(M, K, N_))
-            return y
-        self.op(seg, "pw_fwd", dtype=self.code, M=M, K=K, N=N_, x=x, w=w, y=y, pro=pro or dict(mode=0),
-                residual=residual, stats=stats_bn.stats if stats_bn is not None else None, w_frag=wfrag, form=1)
+            extra = dict(stats=None, epi=stats_bn.epi(epi_mode), **self._split(M, K, N_))
+        else:
+            wfrag = (self.pack(wparam, cabi.MDS_PACK_FRAG_OI, N_, K, 1)
+                     if wt is None and self.lib.fn["pw_fwd_wants_frag"](int(M), int(K), int(N_), int(self.code), 0) else None)
+            extra = dict(stats=stats_bn.stats if stats_bn is not None else None, w_frag=wfrag, form=1)
+        self.op(seg, "pw_fwd", dtype=self.code, M=M, K=K, N=N_, x=x, w=w, y=y, pro=pro or NO_PRO, residual=residual, **extra)
         if stats_bn is not None:
-            stats_bn.finalize(self, seg)
+            stats_bn.finalize(self, seg)      # (inference plans: the eval table)
         return y
+
+    def _conv_fwd(self, seg, geom, taps, A, B, x, w, y, stride=1, os=1, oy0=0, ox0=0, pro=None, residual=None, stats=None, **extra):
+        """one mds_conv_fwd launch (a data gradient is one too): `geom` = N, IH, IW, Cin, OH, OW, Cout, `taps` = geometry.py's lists"""
+        self.op(seg, "conv_fwd", dtype=self.code, **geom, A=A, B=B, oy0=oy0, ox0=ox0, os=os, **_taps_kw(taps, stride), x=x, w=w, y=y,
+                pro=pro or NO_PRO, residual=residual, stats=stats, **extra)
 
     def _conv(self, seg, x, pro, N, IH, IW, Cin, Cout, stride, wparam, bn_mod):
         """inference plans: the output is stored as silu(bn(y)) (mds_epi_t); consumers then read it without a prologue"""
         OH, OW, pt, pl = geo.conv_geometry(IH, IW, stride)
+        geom = dict(N=N, IH=IH, IW=IW, Cin=Cin, OH=OH, OW=OW, Cout=Cout)
         bn = BNL(self, bn_mod, Cout, N * OH * OW)
-        dy, dx, wi = geo.taps_fwd(pt, pl)
         y = self.act(N * OH * OW, Cout)
         w = self.pack(wparam, cabi.MDS_PACK_OI, Cout, Cin, 9)
-        extra = dict(stats=bn.stats)
-        if self.eval_epilogues:
-            extra = dict(stats=None, epi=dict(_struct="mds_epi_t", mode=EPI_BN_SILU, scale=bn.scale, shift=bn.shift))
-        self.op(seg, "conv_fwd", dtype=self.code, N=N, IH=IH, IW=IW, Cin=Cin, OH=OH, OW=OW, Cout=Cout, A=OH, B=OW,
-                oy0=0, ox0=0, os=1, **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=x, w=w, y=y,
-                pro=pro or dict(mode=0), residual=None, **extra)
+        self._conv_fwd(seg, geom, geo.taps_fwd(pt, pl), OH, OW, x, w, y, stride=stride, pro=pro, **bn.sink(self))
         bn.finalize(self, seg)
-        return y, bn, OH, OW, (pt, pl)
+        return y, bn, geom, (pt, pl)
 
-    def _conv_dgrad(self, seg, dyb, N, IH, IW, Cin, Cout, stride, wparam, pads, residual, head=None):
+    def _conv_wgrad(self, seg, x, pro, geom, stride, pads, dyb, wparam):
+        self.op(seg, "conv_wgrad", dtype=self.code, **geom, **_taps_kw(geo.taps_fwd(*pads), stride), x=x, dyt=dyb, dw=self.grad(wparam),
+                pro=pro or NO_PRO)
+
+    def _conv_dgrad(self, seg, dyb, geom, stride, wparam, pads, residual, head=None):
         """grad wrt the conv input ([N][IH][IW][Cin]) from dy ([N][OH][OW][Cout]).  `head`: the BatchNorm backward that consumes
         this gradient directly (the block below's last BatchNorm) - where the launch goes to a kernel that implements
         mds_poststat_t (k_c3.hip: mds_conv_dgrad_post_ok) its sums CAN be taken in the epilogue and the Grad says so.
         MDS_FUSE_CONV_POST=1 switches that on (four bn_bwd_reduce launches and 0.75 GB per step less, parity-green) - measured
         0.05 - 0.1 ms per step SLOWER than the separate reduce passes (round 6, profiles/LOG.md), so the default leaves it off."""
-        OH, OW, _, _ = geo.conv_geometry(IH, IW, stride)
+        N, IH, IW, Cin, OH, OW, Cout = (geom[k] for k in ("N", "IH", "IW", "Cin", "OH", "OW", "Cout"))
         w = self.pack(wparam, cabi.MDS_PACK_IO_FLIP, Cout, Cin, 9)
         dxb = self.act(N * IH * IW, Cin)
-        common = dict(dtype=self.code, N=N, IH=OH, IW=OW, Cin=Cout, OH=IH, OW=IW, Cout=Cin, wtaps=9, x=dyb, w=w,
-                      y=dxb, pro=dict(mode=0), residual=residual, stats=None)
-        fused = None
-        if (head is not None and (head["mode"] != POST_MASK or head["rpg"] == IH * IW)
-                and (head["mode"] != POST_SILU or self.dev.fuse_conv_post_silu)
+        back = dict(N=N, IH=OH, IW=OW, Cin=Cout, OH=IH, OW=IW, Cout=Cin)      # the forward launch's, input and output swapped
+        extra, fused = {}, None
+        if (head is not None and (head["mode"] != cabi.MDS_POST_MASK or head["rpg"] == IH * IW)
+                and (head["mode"] != cabi.MDS_POST_SILU or self.dev.fuse_conv_post_silu)
                 and self.dev.fuse_conv_post
                 and self.lib.fn["conv_dgrad_post_ok"](int(self.code), int(N), int(IH), int(IW), int(Cin), int(Cout), int(stride), int(residual is not None))):
-            common["post"] = head["bn"].post(head)
+            extra["post"] = head["bn"].post(head)
             fused = head["bn"]
         if stride == 1:
-            dy, dx, wi = geo.taps_dgrad_s1()
-            self.op(seg, "conv_fwd", A=IH, B=IW, oy0=0, ox0=0, os=1, **{"is": 1}, ntaps=9, dy=dy, dx=dx, wi=wi, **common)
+            launches = [dict(taps=geo.taps_dgrad_s1(), A=IH, B=IW)]
         else:
             assert residual is None
             par = []
             for py in range(2):
                 for px in range(2):
-                    dy, dx, wi = geo.taps_dgrad_s2(py, px, pads[0], pads[1])
+                    taps = geo.taps_dgrad_s2(py, px, pads[0], pads[1])
                     A, B_ = (IH - py + 1) // 2, (IW - px + 1) // 2
-                    assert dy and A > 0 and B_ > 0
-                    par.append((py, px, dy, dx, wi, A, B_))
+                    assert taps[0] and A > 0 and B_ > 0
+                    par.append(dict(taps=taps, A=A, B=B_, oy0=py, ox0=px, os=2))
             if Cout % 32 == 0:       # the four parities as tap groups of ONE launch: dy is read once
-                self.op(seg, "conv_fwd", A=max(p[5] for p in par), B=max(p[6] for p in par), oy0=0, ox0=0, os=2, **{"is": 1},
-                        ntaps=sum(len(p[2]) for p in par), dy=sum((p[2] for p in par), []), dx=sum((p[3] for p in par), []),
-                        wi=sum((p[4] for p in par), []), ngroups=4, g_ntaps=[len(p[2]) for p in par],
-                        g_oy0=[p[0] for p in par], g_ox0=[p[1] for p in par], g_A=[p[5] for p in par], g_B=[p[6] for p in par],
-                        **common)
+                col = lambda k: [p[k] for p in par]
+                launches = [dict(taps=tuple(sum((p["taps"][j] for p in par), []) for j in range(3)), A=max(col("A")), B=max(col("B")), os=2,
+                                 ngroups=4, g_ntaps=[len(p["taps"][0]) for p in par], g_oy0=col("oy0"), g_ox0=col("ox0"), g_A=col("A"),
+                                 g_B=col("B"))]
             else:
                 assert fused is None
-                for (py, px, dy, dx, wi, A, B_) in par:
-                    self.op(seg, "conv_fwd", A=A, B=B_, oy0=py, ox0=px, os=2, **{"is": 1}, ntaps=len(dy), dy=dy, dx=dx,
-                            wi=wi, **common)
+                launches = par
+        for kw in launches:
+            self._conv_fwd(seg, back, x=dyb, w=w, y=dxb, residual=residual, **kw, **extra)
         return Grad(dxb, fused)
 
     def _pw_bwd(self, seg, xin, pro, M, K, N_, wparam, dy, need_dx, residual=None, frozen=False, head=None):
         """wgrad (+ dgrad) of a 1x1 conv y[M][N] = pro(x)[M][K] w^T from the materialised dy; `head`: take the next BatchNorm
         backward's sums in the dgrad epilogue."""
         if not frozen:
-            self.op(seg, "pw_wgrad", dtype=self.code, M=M, K=K, N=N_, x=xin, dy=dy, dw=self.grad(wparam), pro=pro or dict(mode=0))
+            self.op(seg, "pw_wgrad", dtype=self.code, M=M, K=K, N=N_, x=xin, dy=dy, dw=self.grad(wparam), pro=pro or NO_PRO)
         if not need_dx:
             return None
         wt = self.pack(wparam, cabi.MDS_PACK_IO_FLIP, N_, K, 1)       # [K][N]
@@ -520,60 +567,63 @@ class Plan:
             extra["post"] = head["bn"].post(head)
         if self.lib.fn["pw_fwd_wants_frag"](int(M), int(N_), int(K), int(self.code), 1):
             extra["w_frag"] = self.pack(wparam, cabi.MDS_PACK_FRAG_IO, N_, K, 1)
-        self.op(seg, "pw_fwd", dtype=self.code, M=M, K=N_, N=K, x=dy, w=wt, y=dx, pro=dict(mode=0), residual=residual, stats=None, form=2, **extra)
+        self.op(seg, "pw_fwd", dtype=self.code, M=M, K=N_, N=K, x=dy, w=wt, y=dx, pro=NO_PRO, residual=residual, stats=None, form=2, **extra)
         return Grad(dx, head["bn"] if head is not None else None)
 
-    def _ir_block_eval(self, fseg, blk, bn1, bn2, bn3, xin, N, T, IH, IW, OH, OW, pt, pl, stride, groups, has_skip, kt):
+    def _dw_fwd(self, seg, dwg, x, w, y, pro=None, stats=None, **extra):
+        """one mds_dw_fwd launch; `dwg` = N, T, IH, IW, C, OH, OW, stride, pad_t, pad_l, kt - the geometry mds_dw_bwd repeats"""
+        self.op(seg, "dw_fwd", dtype=self.code, **dwg, x=x, w=w, y=y, pro=pro or NO_PRO, stats=stats, **extra)
+
+    def _se_fc_fwd(self, seg, se, groups, C_, pooled, hidden, gate, w2t):
+        """the squeeze-excite gate of `groups` pooled rows: sigmoid(W2 silu(W1 pooled + b1) + b2); w2t = the fp32 [R][C] pack of W2"""
+        self.op(seg, "se_fc_fwd", groups=groups, C=C_, R=se.rd, pooled=pooled, w1=P(se.conv_reduce.weight),
+                b1=P(se.conv_reduce.bias), w2=P(se.conv_expand.weight), b2=P(se.conv_expand.bias), hidden=hidden, gate=gate, w2t=w2t)
+
+    def _bn_res(self, seg, bn, y, act, mask=None, rpg=0, shortcut=None):
+        """materialise act(bn(y)) * DropPath mask + shortcut - a block output, which two consumers read; -> the new buffer"""
+        out = self.act(bn.count, bn.C)
+        self.op(seg, "bn_res", dtype=self.code, M=bn.count, C=bn.C, y=y, scale=bn.scale, shift=bn.shift, act=act, mask=mask,
+                rows_per_group=rpg, shortcut=shortcut, out=out)
+        return out
+
+    def _ir_block_eval(self, fseg, blk, bn1, bn2, bn3, xin, dwg, groups, has_skip):
         """Inference form of the inverted-residual block: the BatchNorm coefficients are known before any
         producer runs, so every producer stores its ACTIVATED output (mds_epi_t) - no BN+SiLU prologue in the consumers
         (the depthwise kernel re-evaluated it 1.33x per element), no activation copy in the pooling pass, no bn_res launch."""
         cin, mid, cout = blk.cin, blk.mid, blk.cout
-        Min, Mout = N * T * IH * IW, N * T * OH * OW
+        Min, Mout = bn1.count, bn2.count
         rpg = Mout // groups
-        for bn in (bn1, bn2, bn3):
-            bn.finalize(self, fseg)         # -> the plan's eval-BatchNorm table (one launch per forward)
-        def epi(bn, mode):
-            return dict(_struct="mds_epi_t", mode=mode, scale=bn.scale, shift=bn.shift)
+        for bn in (bn1, bn2, bn3):          # -> the plan's eval-BatchNorm table (one launch per forward), in this order: _pw finalizes
+            bn.finalize(self, fseg)         #    bn1 / bn3 again below, which adds nothing (an eval-mode finalize is idempotent)
         w1 = self.pack(blk.conv_pw.weight, cabi.MDS_PACK_OI, mid, cin, 1)
-        if self.eval_fusion and kt == 1 and T == 1 and mid % 16 == 0 and cin % 8 == 0:
+        extra = {}
+        if self.eval_fusion and dwg["kt"] == 1 and dwg["T"] == 1 and mid % 16 == 0 and cin % 8 == 0:
             # the expansion runs inside the depthwise launch: y1 = silu(bn1(xin w1^T)) lives in LDS only (k_dwx.hip)
-            a1, expand = None, dict(_struct="mds_expand_t", x=xin, w=w1, cin=cin, scale=bn1.scale, shift=bn1.shift)
+            a1, extra["expand"] = None, dict(_struct="mds_expand_t", x=xin, w=w1, cin=cin, scale=bn1.scale, shift=bn1.shift)
         else:
-            a1, expand = self.act(Min, mid), None
-            self.op(fseg, "pw_fwd", dtype=self.code, M=Min, K=cin, N=mid, x=xin, w=w1, y=a1, pro=dict(mode=0), residual=None,
-                    stats=None, epi=epi(bn1, EPI_BN_SILU), **self._split(Min, cin, mid))
+            a1 = self._pw(fseg, xin, Min, cin, mid, None, stats_bn=bn1, wt=w1, epi_mode=cabi.MDS_EPI_BN_SILU)
         a2 = self.act(Mout, mid)
         R = blk.se.rd
         pooled, hidden, gate = self.zero_fwd64(groups * mid), self.f32(groups * R), self.f32(groups * mid)
         # the depthwise pass stores the activation AND takes its per-image channel means (the squeeze-excite input): no se_pool launch
-        fuse_pool = groups == N and self.dev.eval_pool
+        fuse_pool = groups == dwg["N"] and self.dev.eval_pool
         se = blk.se
         w2t = self.pack(se.conv_expand.weight, cabi.MDS_PACK_IO_F32, mid, R, 1)
         # ... and, with eval_se_fusion, the block that completes an image's means also computes its gate: no se_fc_fwd launch
         fuse_se = (self.eval_se_fusion and fuse_pool and mid % 4 == 0 and mid <= cabi.MDS_SE_TAIL_CMAX
                    and R <= cabi.MDS_SE_TAIL_RMAX)
-        extra = {}
-        if expand is not None:
-            extra["expand"] = expand
         if fuse_se:
             extra["se"] = dict(_struct="mds_se_tail_t", R=R, w1=P(se.conv_reduce.weight), b1=P(se.conv_reduce.bias), w2t=w2t,
-                               b2=P(se.conv_expand.bias), hidden=hidden, gate=gate, ticket=self._se_tickets(groups))
-        self.op(fseg, "dw_fwd", dtype=self.code, N=N, T=T, IH=IH, IW=IW, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt,
-                pad_l=pl, kt=kt, x=a1, w=P(blk.conv_dw.weight), y=a2, pro=dict(mode=0), stats=None, epi=epi(bn2, EPI_BN_SILU),
-                pool=pooled if fuse_pool else None, pool_inv=1.0 / rpg if fuse_pool else 0.0, **extra)
+                               b2=P(se.conv_expand.bias), hidden=hidden, gate=gate, ticket=self._tickets("_se_ticket", groups))
+        self._dw_fwd(fseg, dwg, a1, P(blk.conv_dw.weight), a2, epi=bn2.epi(), pool=pooled if fuse_pool else None,
+                     pool_inv=1.0 / rpg if fuse_pool else 0.0, **extra)
         if not fuse_pool:
             self.op(fseg, "se_pool", dtype=self.code, groups=groups, rows_per_group=rpg, C=mid, y=a2, scale=None, shift=None,
                     pooled=pooled, act=None)
         if not fuse_se:
-            self.op(fseg, "se_fc_fwd", groups=groups, C=mid, R=R, pooled=pooled, w1=P(se.conv_reduce.weight),
-                    b1=P(se.conv_reduce.bias), w2=P(se.conv_expand.weight), b2=P(se.conv_expand.bias), hidden=hidden, gate=gate,
-                    w2t=w2t)
-        xout = self.act(Mout, cout)
-        self.op(fseg, "pw_fwd", dtype=self.code, M=Mout, K=mid, N=cout, x=a2,
-                w=self.pack(blk.conv_pwl.weight, cabi.MDS_PACK_OI, cout, mid, 1), y=xout,
-                pro=dict(mode=PRO_GATE, scale=None, shift=None, gate=gate, rows_per_group=rpg),
-                residual=xin if has_skip else None, stats=None, epi=epi(bn3, EPI_AFFINE), **self._split(Mout, mid, cout))
-        return xout, OH, OW
+            self._se_fc_fwd(fseg, se, groups, mid, pooled, hidden, gate, w2t)
+        return self._pw(fseg, a2, Mout, mid, cout, blk.conv_pwl.weight, pro=gate_pro(gate, rpg), stats_bn=bn3,
+                        residual=xin if has_skip else None, epi_mode=cabi.MDS_EPI_AFFINE)
 
     # -- inverted-residual block (2D: T=1, kt=1 ; 3D: kt=3), shared by encoder stages 3-5 and conv3d_encoder
     def _ir_block(self, fseg, recs, blk, bn1m, bn2m, bn3m, xin, N, T, IH, IW, stride, groups, has_skip, frozen):
@@ -582,14 +632,14 @@ class Plan:
         OH, OW, pt, pl = geo.conv_geometry(IH, IW, stride)
         Min, Mout = N * T * IH * IW, N * T * OH * OW
         rpg = Mout // groups
+        dwg = dict(N=N, T=T, IH=IH, IW=IW, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt, pad_l=pl, kt=kt)
         bn1, bn2, bn3 = BNL(self, bn1m, mid, Min), BNL(self, bn2m, mid, Mout), BNL(self, bn3m, cout, Mout)
         if self.eval_epilogues and (kt == 1 or T == 5):
-            return self._ir_block_eval(fseg, blk, bn1, bn2, bn3, xin, N, T, IH, IW, OH, OW, pt, pl, stride, groups, has_skip, kt)
+            return self._ir_block_eval(fseg, blk, bn1, bn2, bn3, xin, dwg, groups, has_skip), OH, OW
         y1 = self._pw(fseg, xin, Min, cin, mid, blk.conv_pw.weight, stats_bn=bn1)
         y2 = self.act(Mout, mid)
         wdw = P(blk.conv_dw.weight)
-        self.op(fseg, "dw_fwd", dtype=self.code, N=N, T=T, IH=IH, IW=IW, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt,
-                pad_l=pl, kt=kt, x=y1, w=wdw, y=y2, pro=bn1.pro(), stats=bn2.stats)
+        self._dw_fwd(fseg, dwg, y1, wdw, y2, pro=bn1.pro(), stats=bn2.stats)
         bn2.finalize(self, fseg)
         R = blk.se.rd
         pooled, hidden, gate = self.zero_fwd64(groups * mid), self.f32(groups * R), self.f32(groups * mid)
@@ -601,35 +651,27 @@ class Plan:
         a2 = self.act(Mout, mid) if keep_act else y2
         self.op(fseg, "se_pool", dtype=self.code, groups=groups, rows_per_group=rpg, C=mid, y=y2, scale=bn2.scale,
                 shift=bn2.shift, pooled=pooled, act=a2 if keep_act else None)
-        gate_pro = (dict(mode=PRO_GATE, scale=None, shift=None, gate=gate, rows_per_group=rpg) if keep_act else
-                    dict(mode=PRO_BN_GATE, scale=bn2.scale, shift=bn2.shift, gate=gate, rows_per_group=rpg))
+        pro2 = gate_pro(gate, rpg, None if keep_act else bn2)
         se = blk.se
         w2t = self.pack(se.conv_expand.weight, cabi.MDS_PACK_IO_F32, mid, R, 1)    # [R][mid], fp32
-        self.op(fseg, "se_fc_fwd", groups=groups, C=mid, R=R, pooled=pooled, w1=P(se.conv_reduce.weight),
-                b1=P(se.conv_reduce.bias), w2=P(se.conv_expand.weight), b2=P(se.conv_expand.bias), hidden=hidden, gate=gate,
-                w2t=w2t)
-        y3 = self._pw(fseg, a2, Mout, mid, cout, blk.conv_pwl.weight, pro=gate_pro, stats_bn=bn3)
+        self._se_fc_fwd(fseg, se, groups, mid, pooled, hidden, gate, w2t)
+        y3 = self._pw(fseg, a2, Mout, mid, cout, blk.conv_pwl.weight, pro=pro2, stats_bn=bn3)
         mask = self.mask(groups, blk.dpr) if has_skip else None
-        xout = self.act(Mout, cout)
-        self.op(fseg, "bn_res", dtype=self.code, M=Mout, C=cout, y=y3, scale=bn3.scale, shift=bn3.shift, act=0, mask=mask,
-                rows_per_group=rpg, shortcut=xin if has_skip else None, out=xout)
+        xout = self._bn_res(fseg, bn3, y3, act=0, mask=mask, rpg=rpg, shortcut=xin if has_skip else None)
         self.taps.append(dict(tag=f"{fseg}.ir{len(self.taps)}", buf=xout, bn=None, rows=Mout, C=cout))
 
         def bwd(seg, dout, nxt_head):
-            g3 = gsrc(G_MASK, dout.buf, mask=mask, rpg=rpg) if mask is not None else gsrc(G_PLAIN, dout.buf)
+            g3, reduce = bn3.g_res(dout, mask, rpg)
             dy3 = self.act(Mout, cout)      # (the sums may have been taken by the producer of dout, a 1x1 data-gradient GEMM's epilogue)
-            bn3.backward(self, seg, g3, y3, dy3, reduce=dout.reduced is not bn3, frozen=frozen)
-            u2 = self._pw_bwd(seg, a2, gate_pro, Mout, mid, cout, blk.conv_pwl.weight, dy3, True, frozen=frozen).buf
+            bn3.backward(self, seg, g3, y3, dy3, reduce=reduce, frozen=frozen)
+            u2 = self._pw_bwd(seg, a2, pro2, Mout, mid, cout, blk.conv_pwl.weight, dy3, True, frozen=frozen).buf
             dgate, dpool = self.zero_bwd64(groups * mid), self.f32(groups * mid)
             nblk = self.lib.fn["se_bwd_reduce_blocks"](rpg, mid)
             bnsums = self.f32(groups * nblk * 4 * mid)
             self.op(seg, "se_bwd_reduce", dtype=self.code, groups=groups, rows_per_group=rpg, C=mid, u=u2, y=y2,
                     scale=bn2.scale, shift=bn2.shift, dgate=dgate, mean=bn2.mean, rstd=bn2.rstd, bnsums=bnsums)
-            if frozen:
-                sg = [self.f32(se.conv_reduce.weight.numel()), self.f32(R), self.f32(se.conv_expand.weight.numel()), self.f32(mid)]
-            else:
-                sg = [self.grad(se.conv_reduce.weight), self.grad(se.conv_reduce.bias), self.grad(se.conv_expand.weight),
-                      self.grad(se.conv_expand.bias)]
+            sg = [self.f32(p.numel()) if frozen else self.grad(p)
+                  for p in (se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias)]
             sekw = dict(groups=groups, C=mid, R=R, rows_per_group=rpg, dgate=dgate, gate=gate, hidden=hidden,
                         pooled=pooled, w1=P(se.conv_reduce.weight), w2=P(se.conv_expand.weight), dpooled=dpool,
                         scratch=self.f32(groups * R), dw1=sg[0], db1=sg[1], dw2=sg[2], db2=sg[3],
@@ -640,19 +682,17 @@ class Plan:
             else:
                 self.op(seg, "se_fc_bwd_params", _struct="mds_se_fc_bwd_args", **sekw)
             dy2 = self.act(Mout, mid)
-            bn2.backward(self, seg, gsrc(G_SE, u2, gate=gate, dpooled=dpool, rpg=rpg), y2, dy2, reduce=False, frozen=frozen)
+            bn2.backward(self, seg, gsrc(cabi.MDS_G_SE_SILU, u2, gate=gate, dpooled=dpool, rpg=rpg), y2, dy2, reduce=False, frozen=frozen)
             g1 = self.act(Min, mid)
-            self.op(seg, "dw_bwd", dtype=self.code, N=N, T=T, IH=IH, IW=IW, C=mid, OH=OH, OW=OW, stride=stride, pad_t=pt,
-                    pad_l=pl, kt=kt, x=y1, dy=dy2, w=wdw, g=g1, dw=self.f32(mid * kt * 9) if frozen else self.grad(blk.conv_dw.weight),
+            self.op(seg, "dw_bwd", dtype=self.code, **dwg, x=y1, dy=dy2, w=wdw, g=g1,
+                    dw=self.f32(mid * kt * 9) if frozen else self.grad(blk.conv_dw.weight),
                     pro=bn1.pro(), mean=bn1.mean, rstd=bn1.rstd, stats=bn1.bstats)
             dy1 = self.act(Min, mid)
-            bn1.backward(self, seg, gsrc(G_PLAIN, g1), y1, dy1, reduce=False, frozen=frozen)
+            bn1.backward(self, seg, gsrc(cabi.MDS_G_PLAIN, g1), y1, dy1, reduce=False, frozen=frozen)
             return self._pw_bwd(seg, xin, None, Min, cin, mid, blk.conv_pw.weight, dy1, True,
                                 residual=dout.buf if has_skip else None, frozen=frozen, head=nxt_head)
 
-        bwd.head = bn3.head(y3, POST_MASK if mask is not None else POST_PLAIN, mask, rpg)
-        bwd.lo = self._lo(blk)
-        recs.append(bwd)
+        recs.append(Bwd(bwd, self._lo(blk), bn3.head(y3, cabi.MDS_POST_MASK if mask is not None else cabi.MDS_POST_PLAIN, mask, rpg)))
         return xout, OH, OW
 
     # -- 2D: stem + 21 encoder blocks + conv2d_projection  (forward_2d, :210-219)
@@ -664,6 +704,7 @@ class Plan:
         y0 = self.act(N * OH * OW, 32)
         bn0 = BNL(self, enc.bn1, 32, N * OH * OW)
         wst = self.pack(enc.conv_stem.weight, cabi.MDS_PACK_STEM, 32, 27, 1)
+        stem = dict(dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl)      # what every stem launch starts with
         extra = {}
         if self.ingest is not None:      # raw frames: [nsrc][3][src_h][src_w] uint8, images beyond nsrc are the mirrored TTA copies
             src_h, src_w, nsrc = self.ingest
@@ -671,47 +712,33 @@ class Plan:
             self.x_u8 = self._own(nsrc * 3 * src_h * src_w, torch.uint8)
             extra["ingest"] = dict(_struct="mds_ingest_t", u8=self.x_u8, nsrc=nsrc, src_h=src_h, src_w=src_w,
                                    pad_top=(H - src_h) // 2, pad_left=(W - src_w) // 2, scale=1.0 / 255.0)
-        if self.eval_epilogues:
-            extra.update(stats=None, epi=dict(_struct="mds_epi_t", mode=EPI_BN_SILU, scale=bn0.scale, shift=bn0.shift))
-        else:
-            extra.update(stats=bn0.stats)
-        self.op("f2d", "stem_fwd", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
-                x=None if self.ingest is not None else self.x_in, w=wst, y=y0, **extra)
+        self.op("f2d", "stem_fwd", **stem, x=None if self.ingest is not None else self.x_in, w=wst, y=y0, **extra, **bn0.sink(self))
         bn0.finalize(self, "f2d")
-
-        def stem_dgrad(seg, **dy):
-            """the gradient of the frames, after the weight gradient: the stem's dy goes to both kernels the same way (bf16: formed
-            on load by each, 2 x 602 MB read at batch 4 against 602 + 301 written + 2 x 301 read with a materialised dy0)"""
-            if self.input_grad:
-                self.op(seg, "stem_dgrad", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl, w=wst,
-                        dx=self.dx, **dy)
 
         def stem_bwd(seg, u0, nxt_head):
             if fr:
                 return None
             # (u0.reduced is bn0: the first 3x3 layer's data gradient stored g = u * silu'(z) and took the sums - k_c3.hip, POST_SILU)
-            g0 = gsrc(G_PLAIN, u0.buf) if u0.reduced is bn0 else gsrc(G_SILU, u0.buf)
+            g0, reduce = bn0.g_act(u0)
             if self.tdt == torch.bfloat16 and self.dev.stem_dyp:
                 # the stem's BatchNorm-backward apply pass would only feed the weight gradient (and, when the frames require grad, the
                 # data gradient), which form dy = A*u*silu'(z) + B*y + D on load instead (no 0.9 GB apply launch at the very end of the step)
-                if u0.reduced is not bn0:
+                if reduce:
                     bn0.bwd_reduce(self, seg, g0, y0)
                 bn0.bwd_finalize(self, seg)
-                self.op(seg, "stem_wgrad", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
-                        x=self.x_in, dy=None, dw=self.grad(enc.conv_stem.weight),
-                        dyp=dict(_struct="mds_dyp_t", mode=1, g=g0, y=y0, bn=bn0.buf, lin=bn0.lin))
-                stem_dgrad(seg, dy=None, dyp=dict(_struct="mds_dyp_t", mode=1, g=g0, y=y0, bn=bn0.buf, lin=bn0.lin))
-                return None
-            dy0 = self.act(N * OH * OW, 32)
-            bn0.backward(self, seg, g0, y0, dy0, reduce=u0.reduced is not bn0)
-            self.op(seg, "stem_wgrad", dtype=self.code, N=N, H=H, W=W, OH=OH, OW=OW, Cout=32, pad_t=pt, pad_l=pl,
-                    x=self.x_in, dy=dy0, dw=self.grad(enc.conv_stem.weight))
-            stem_dgrad(seg, dy=dy0)
+                dy = dict(dy=None, dyp=dict(_struct="mds_dyp_t", mode=1, g=g0, y=y0, bn=bn0.buf, lin=bn0.lin))
+            else:
+                dy0 = self.act(N * OH * OW, 32)
+                bn0.backward(self, seg, g0, y0, dy0, reduce=reduce)
+                dy = dict(dy=dy0)
+            self.op(seg, "stem_wgrad", **stem, x=self.x_in, dw=self.grad(enc.conv_stem.weight), **dy)
+            # the gradient of the frames, after the weight gradient: the stem's dy goes to both kernels the same way (bf16: formed
+            # on load by each, 2 x 602 MB read at batch 4 against 602 + 301 written + 2 x 301 read with a materialised dy0)
+            if self.input_grad:
+                self.op(seg, "stem_dgrad", **stem, w=wst, dx=self.dx, **dy)
             return None
 
-        stem_bwd.head = bn0.head(y0, POST_SILU)
-        stem_bwd.lo = self._lo(enc.conv_stem, enc.bn1)
-        recs.append(stem_bwd)
+        recs.append(Bwd(stem_bwd, self._lo(enc.conv_stem, enc.bn1), bn0.head(y0, cabi.MDS_POST_SILU)))
         cur, cur_bn, ch, cw = y0, (None if self.eval_epilogues else bn0), OH, OW      # cur_bn != None: `cur` is a raw tensor read through BN+SiLU
         for blk in enc.block_list():
             if blk.kind == "cn":
@@ -728,32 +755,27 @@ class Plan:
         cenc = enc.feature_info[-1]["num_chs"]
         bnp = BNL(self, m.conv2d_projection[1], cf, M)
         if self.eval_epilogues:          # inference: BN + SiLU in the projection's epilogue
-            feat = self._pw("f2d", cur, M, cenc, cf, m.conv2d_projection[0].weight, stats_bn=bnp, epi_mode=EPI_BN_SILU)
+            feat = self._pw("f2d", cur, M, cenc, cf, m.conv2d_projection[0].weight, stats_bn=bnp, epi_mode=cabi.MDS_EPI_BN_SILU)
             return feat, ch, cw
         yp = self._pw("f2d", cur, M, cenc, cf, m.conv2d_projection[0].weight, stats_bn=bnp)
-        feat = self.act(M, cf)
-        self.op("f2d", "bn_res", dtype=self.code, M=M, C=cf, y=yp, scale=bnp.scale, shift=bnp.shift, act=1, mask=None,
-                rows_per_group=0, shortcut=None, out=feat)
+        feat = self._bn_res("f2d", bnp, yp, act=1)
         self.taps.append(dict(tag="f2d.proj", buf=feat, bn=None, rows=M, C=cf))
         xenc = cur
 
         def proj_bwd(seg, dfeat, nxt_head):
             dyp = self.act(M, cf)
-            if dfeat.reduced is bnp:      # the 3D tail's last data-gradient GEMM stored g = dfeat*silu'(z) and took the sums
-                bnp.backward(self, seg, gsrc(G_PLAIN, dfeat.buf), yp, dyp, reduce=False)
-            else:
-                bnp.backward(self, seg, gsrc(G_SILU, dfeat.buf), yp, dyp)
+            g, reduce = bnp.g_act(dfeat)      # (took the sums: the 3D tail's last data-gradient GEMM)
+            bnp.backward(self, seg, g, yp, dyp, reduce=reduce)
             return self._pw_bwd(seg, xenc, None, M, cenc, cf, m.conv2d_projection[0].weight, dyp, need_dx=not fr, head=nxt_head)
 
-        proj_bwd.head = bnp.head(yp, POST_SILU)
-        proj_bwd.lo = self._lo(m.conv2d_projection)
-        recs.append(proj_bwd)
+        recs.append(Bwd(proj_bwd, self._lo(m.conv2d_projection), bnp.head(yp, cabi.MDS_POST_SILU)))
         return feat, ch, cw
 
     def _cn_block(self, recs, blk, xin, xin_bn, N, IH, IW, fr):
         assert not blk.has_skip and (xin_bn is not None or self.eval_epilogues)
-        y, bn1, OH, OW, pads = self._conv("f2d", xin, xin_bn.pro() if xin_bn is not None else None, N, IH, IW, blk.cin, blk.cout,
-                                          blk.stride, blk.conv.weight, blk.bn1)
+        y, bn1, geom, pads = self._conv("f2d", xin, xin_bn.pro() if xin_bn is not None else None, N, IH, IW, blk.cin, blk.cout,
+                                        blk.stride, blk.conv.weight, blk.bn1)
+        OH, OW = geom["OH"], geom["OW"]
         if self.eval_epilogues:
             return y, None, OH, OW       # activated output, no backward
         self.taps.append(dict(tag=f"f2d.cn{len(self.taps)}", buf=y, bn=bn1, rows=N * OH * OW, C=blk.cout))
@@ -762,23 +784,13 @@ class Plan:
             if fr:
                 return None
             dy_ = self.act(N * OH * OW, blk.cout)
-            if u.reduced is bn1:      # the producer (a 3x3 data gradient of k_c3.hip) stored g = u * silu'(z) and took the sums
-                bn1.backward(self, seg, gsrc(G_PLAIN, u.buf), y, dy_, reduce=False)
-            else:
-                bn1.backward(self, seg, gsrc(G_SILU, u.buf), y, dy_)
-            self._conv_wgrad(seg, xin, xin_bn.pro(), N, IH, IW, blk.cin, OH, OW, blk.cout, blk.stride, pads, dy_, blk.conv.weight)
-            return self._conv_dgrad(seg, dy_, N, IH, IW, blk.cin, blk.cout, blk.stride, blk.conv.weight, pads, None, head=nxt_head)
+            g, reduce = bn1.g_act(u)      # (took the sums: the producer, a 3x3 data gradient of k_c3.hip)
+            bn1.backward(self, seg, g, y, dy_, reduce=reduce)
+            self._conv_wgrad(seg, xin, xin_bn.pro(), geom, blk.stride, pads, dy_, blk.conv.weight)
+            return self._conv_dgrad(seg, dy_, geom, blk.stride, blk.conv.weight, pads, None, head=nxt_head)
 
-        bwd.head = bn1.head(y, POST_SILU)
-        bwd.lo = self._lo(blk)
-        recs.append(bwd)
+        recs.append(Bwd(bwd, self._lo(blk), bn1.head(y, cabi.MDS_POST_SILU)))
         return y, bn1, OH, OW
-
-    def _conv_wgrad(self, seg, x, pro, N, IH, IW, Cin, OH, OW, Cout, stride, pads, dyb, wparam):
-        dy, dx, wi = geo.taps_fwd(pads[0], pads[1])
-        self.op(seg, "conv_wgrad", dtype=self.code, N=N, IH=IH, IW=IW, Cin=Cin, OH=OH, OW=OW, Cout=Cout,
-                **{"is": stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=x, dyt=dyb, dw=self.grad(wparam),
-                pro=pro or dict(mode=0))
 
     def _er_block(self, recs, blk, xin, xin_bn, N, IH, IW, fr):
         cin, mid, cout = blk.cin, blk.mid, blk.cout
@@ -791,49 +803,42 @@ class Plan:
             bn1, bn2 = BNL(self, blk.bn1, mid, M), BNL(self, blk.bn2, cout, M)
             bn1.finalize(self, "f2d")         # -> the plan's eval-BatchNorm table
             bn2.finalize(self, "f2d")
-            dy, dx, wi = geo.taps_fwd(pt, pl)
             xout = self.act(M, cout)
-            self.op("f2d", "conv_fwd", dtype=self.code, N=N, IH=IH, IW=IW, Cin=cin, OH=OH, OW=OW, Cout=mid, A=OH, B=OW,
-                    oy0=0, ox0=0, os=1, **{"is": blk.stride}, ntaps=9, dy=dy, dx=dx, wi=wi, wtaps=9, x=xin,
-                    w=self.pack(blk.conv_exp.weight, cabi.MDS_PACK_OI, mid, cin, 9), y=xout, pro=dict(mode=0),
-                    residual=xin if blk.has_skip else None, stats=None,
-                    epi=dict(_struct="mds_epi_t", mode=EPI_BN_SILU, scale=bn1.scale, shift=bn1.shift),
-                    project=dict(_struct="mds_project_t", w=self.pack(blk.conv_pwl.weight, cabi.MDS_PACK_OI, cout, mid, 1), cout=cout,
-                                 scale=bn2.scale, shift=bn2.shift))
+            wexp = self.pack(blk.conv_exp.weight, cabi.MDS_PACK_OI, mid, cin, 9)
+            wpwl = self.pack(blk.conv_pwl.weight, cabi.MDS_PACK_OI, cout, mid, 1)
+            self._conv_fwd("f2d", dict(N=N, IH=IH, IW=IW, Cin=cin, OH=OH, OW=OW, Cout=mid), geo.taps_fwd(pt, pl), OH, OW, xin, wexp, xout,
+                           stride=blk.stride, residual=xin if blk.has_skip else None, epi=bn1.epi(),
+                           project=dict(_struct="mds_project_t", w=wpwl, cout=cout, scale=bn2.scale, shift=bn2.shift))
             return xout, OH, OW       # (inference plans have no backward closures)
-        ya, bn1, OH, OW, pads = self._conv("f2d", xin, pro_in, N, IH, IW, cin, mid, blk.stride, blk.conv_exp.weight, blk.bn1)
+        ya, bn1, geom, pads = self._conv("f2d", xin, pro_in, N, IH, IW, cin, mid, blk.stride, blk.conv_exp.weight, blk.bn1)
+        OH, OW = geom["OH"], geom["OW"]
         M = N * OH * OW
         bn2 = BNL(self, blk.bn2, cout, M)
         has_skip = blk.has_skip
         assert not has_skip or xin_bn is None
         if self.eval_epilogues:          # inference: BN2 + shortcut in the projection's epilogue, no bn_res launch
             xout = self._pw("f2d", ya, M, mid, cout, blk.conv_pwl.weight, pro=None, stats_bn=bn2,      # ya = silu(bn1(.)) already
-                            residual=xin if has_skip else None, epi_mode=EPI_AFFINE)
+                            residual=xin if has_skip else None, epi_mode=cabi.MDS_EPI_AFFINE)
             return xout, OH, OW       # (inference plans have no backward closures)
         yb = self._pw("f2d", ya, M, mid, cout, blk.conv_pwl.weight, pro=bn1.pro(), stats_bn=bn2)
         mask = self.mask(N, blk.dpr) if has_skip else None
         rpg = OH * OW
-        xout = self.act(M, cout)
-        self.op("f2d", "bn_res", dtype=self.code, M=M, C=cout, y=yb, scale=bn2.scale, shift=bn2.shift, act=0, mask=mask,
-                rows_per_group=rpg, shortcut=xin if has_skip else None, out=xout)
+        xout = self._bn_res("f2d", bn2, yb, act=0, mask=mask, rpg=rpg, shortcut=xin if has_skip else None)
         self.taps.append(dict(tag=f"f2d.er{len(self.taps)}", buf=xout, bn=None, rows=M, C=cout))
 
         def bwd(seg, dout, nxt_head):
             if fr:
                 return None
-            g2 = gsrc(G_MASK, dout.buf, mask=mask, rpg=rpg) if mask is not None else gsrc(G_PLAIN, dout.buf)
+            g2, reduce = bn2.g_res(dout, mask, rpg)
             dya = self.act(M, mid)
             dyb = self.act(M, cout)
-            bn2.backward(self, seg, g2, yb, dyb, reduce=dout.reduced is not bn2)
+            bn2.backward(self, seg, g2, yb, dyb, reduce=reduce)
             ua = self._pw_bwd(seg, ya, bn1.pro(), M, mid, cout, blk.conv_pwl.weight, dyb, True)
-            bn1.backward(self, seg, gsrc(G_SILU, ua.buf), ya, dya)
-            self._conv_wgrad(seg, xin, pro_in, N, IH, IW, cin, OH, OW, mid, blk.stride, pads, dya, blk.conv_exp.weight)
-            return self._conv_dgrad(seg, dya, N, IH, IW, cin, mid, blk.stride, blk.conv_exp.weight, pads,
-                                    dout.buf if has_skip else None, head=nxt_head)
+            bn1.backward(self, seg, gsrc(cabi.MDS_G_SILU, ua.buf), ya, dya)
+            self._conv_wgrad(seg, xin, pro_in, geom, blk.stride, pads, dya, blk.conv_exp.weight)
+            return self._conv_dgrad(seg, dya, geom, blk.stride, blk.conv_exp.weight, pads, dout.buf if has_skip else None, head=nxt_head)
 
-        bwd.head = bn2.head(yb, POST_MASK if mask is not None else POST_PLAIN, mask, rpg)
-        bwd.lo = self._lo(blk)
-        recs.append(bwd)
+        recs.append(Bwd(bwd, self._lo(blk), bn2.head(yb, cabi.MDS_POST_MASK if mask is not None else cabi.MDS_POST_PLAIN, mask, rpg)))
         return xout, OH, OW
 
     # -- 3D: 4 inverted-residual blocks + conv3d_projection  (forward_3d, :221-230).  Channels-last
@@ -853,11 +858,10 @@ class Plan:
 
         def bwd(seg, uq, nxt_head):
             dyq = self.act(M, cq)
-            bnq.backward(self, seg, gsrc(G_SILU, uq.buf), yq, dyq)
+            bnq.backward(self, seg, gsrc(cabi.MDS_G_SILU, uq.buf), yq, dyq)
             return self._pw_bwd(seg, x3, None, M, cf, cq, m.conv3d_projection[0].weight, dyq, True, head=nxt_head)
 
-        bwd.lo = self._lo(m.conv3d_projection)
-        recs.append(bwd)
+        recs.append(Bwd(bwd, self._lo(m.conv3d_projection)))      # (no head: gem_bwd, the producer of uq, is no data-gradient GEMM)
         return yq, bnq
 
     # -- head: GeM over (h, w) for every (b, t, c) + dropout + Linear  (forward_head, :232-237)
@@ -865,7 +869,7 @@ class Plan:
         m = self.m
         cq = m.num_features // S
         F_ = S * cq
-        pro = bnq.pro() if bnq is not None else dict(mode=0)
+        pro = bnq.pro() if bnq is not None else NO_PRO
         gp = m.global_pool
         pooled = self.f32(B * F_)
         self.op("fhead", "gem_fwd", dtype=self.code, groups=B * S, rows_per_group=h * w, C=cq, y=yq, pro=pro, p=P(gp.p),
@@ -889,17 +893,18 @@ class Plan:
                     eps=float(gp.eps), pooled=pooled, dpooled=dpo, u=uq, dp=self.grad(gp.p), accum=self.zero_bwd64(B * S * cq))
             return Grad(uq)
 
-        bwd.lo = self._lo(gp, m.classifier)
-        self._recs["head"].append(bwd)
+        self._recs["head"].append(Bwd(bwd, self._lo(gp, m.classifier)))
 
     # ------------------------------------------------------------------ binding
-    def _finalize(self):
-        dev = self.device
-        # deferred squeeze-excite parameter gradients that no gradient-bucket cut flushed (a builder that called a block's backward
-        # closure on its own): they close the segment they were recorded in
+    def _flush_se(self):
+        """the deferred squeeze-excite parameter gradients of the closures issued so far: one table launch at the end of their segment"""
         for seg in dict.fromkeys(sg for sg, _ in self._se_pending):
             self.op(seg, "se_fc_bwd_params_table", _struct="mds_se_fc_bwd_table_args", _jobs=[kw for sg, kw in self._se_pending if sg == seg])
         self._se_pending = []
+
+    def _finalize(self):
+        dev = self.device
+        self._flush_se()      # what no gradient-bucket cut flushed (a builder that called a block's backward closure on its own)
         self.mask_arena.numel, self.zb64_arena.numel, self.zf64_arena.numel = self._mask_total, self._zb64, self._zf64
         self.mask_arena.tensor = torch.zeros(max(self.mask_arena.numel, 1), dtype=torch.float32, device=dev)
         # everything a pass zeroes lives in ONE buffer per pass (fp64 part first: 8-byte aligned), so that begin_forward /
@@ -940,7 +945,7 @@ class Plan:
             jobs[j].kind, jobs[j].O, jobs[j].I, jobs[j].taps = kind, O, I, taps
             self.pack_max = max(self.pack_max, dst.numel)
         self.pack_table = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
-        self.param_ptrs = tuple(p.data_ptr() for p, *_ in self.pack_jobs)
+        self.param_ptrs = tuple(t.data_ptr() for t in self.weight_tensors())      # what the two tables hold: stale()
         if self.eval_bn:
             BJ = cabi.STRUCTS["mds_bn_eval_job"]
             bj = (BJ * len(self.eval_bn))()
@@ -951,7 +956,6 @@ class Plan:
                 bj[j].out, bj[j].eps, bj[j].C = out.resolve().data_ptr(), float(m.eps), C_
             self.eval_bn_table = torch.frombuffer(bytearray(bytes(bj)), dtype=torch.uint8).to(dev)
             self.eval_bn_maxc = max(e.C for e in self.eval_bn)
-            self.param_ptrs += tuple(t.data_ptr() for e in self.eval_bn for t in (e.mod.weight, e.mod.bias, e.mod.running_mean, e.mod.running_var))
         # bind every recorded launch
         self.bound: Dict[str, list] = {}
         self.costs: Dict[str, list] = {}
@@ -961,7 +965,7 @@ class Plan:
             out = []
             for name, kw in ops:
                 self._input_fields = []
-                st = self._bind(kw.get("_struct", f"mds_{name}_args"), kw)
+                st = self._cstruct(kw.get("_struct", f"mds_{name}_args"), kw)
                 for _, field in self._input_fields:
                     self.input_slots.append((st, field))
                 out.append((name if not kw.get("_side") else name + "@side", self.lib.fn[name], st, C.byref(st)))
@@ -982,7 +986,8 @@ class Plan:
             for name, kw in ops:
                 if name not in self.DET_OPS:
                     continue
-                st = self._bind_dims(kw.get("_struct", f"mds_{name}_args"), kw)
+                # (its scalars only: buffers are not allocated yet, and the geometry queries do not read them)
+                st = self._cstruct(kw.get("_struct", f"mds_{name}_args"), kw, resolve=False)
                 n = int(self.lib.fn[name + "_partial_floats"](C.byref(st)))
                 if n < 0:
                     self.lib.check(n, name + "_partial_floats")
@@ -991,42 +996,34 @@ class Plan:
                 kw["partial"] = dict(_struct="mds_partial_t", buf=ws[side], floats=n)
         self.det_workspace_bytes = 4 * (ws[False].numel + ws[True].numel)
 
-    def _bind_dims(self, struct_name, kw):
-        """the struct of a recorded launch with its scalars only (buffers are not allocated yet): what the geometry queries read"""
+    def _cstruct(self, struct_name, kw, resolve=True):
+        """the C struct of a record, or of a dict nested in one (`_struct` names its type; absent: mds_pro_t).  The leaf policy:
+        resolve - a Lazy or P goes in as its tensor, kept alive by the plan (the frames: noted for bind_input, left null); not resolve
+        (_bind_partials' geometry queries, before memory exists) - every buffer is null.  Keys that begin with `_` are no fields:
+        `_struct`, `_side` (run: to the weight-gradient stream), `_jobs` (a list of mds_se_fc_bwd_args records -> the device-resident
+        array of an mds_se_fc_bwd_table_args; no geometry query has one)."""
         vals = {}
         for k, v in kw.items():
-            if k.startswith("_"):
-                continue
-            if isinstance(v, dict):
-                v = self._bind_dims(v.get("_struct", "mds_pro_t"), v)
-            elif isinstance(v, (Lazy, P)) or hasattr(v, "data_ptr"):
-                v = None
-            vals[k] = v
-        return cabi.make(struct_name, **vals)
-
-    def _bind(self, struct_name, kw):
-        vals = {}
-        for k, v in kw.items():
-            if k in ("_struct", "_side"):
-                continue
-            if k == "_jobs":          # a device-resident array of bound mds_se_fc_bwd_args (mds_se_fc_bwd_table_args)
-                arr = (cabi.STRUCTS["mds_se_fc_bwd_args"] * len(v))()
-                for j, kwj in enumerate(v):
-                    arr[j] = self._bind("mds_se_fc_bwd_args", kwj)
-                tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-                self._keep.append(tab)
-                vals.update(jobs=tab, njobs=len(v), max_rc=max(kwj["R"] * kwj["C"] for kwj in v))
-                continue
-            if isinstance(v, dict):
-                v = self._bind(v.get("_struct", "mds_pro_t"), v)
+            if k[0] == "_":
+                if k == "_jobs" and resolve:
+                    arr = (cabi.STRUCTS["mds_se_fc_bwd_args"] * len(v))()
+                    for j, kwj in enumerate(v):
+                        arr[j] = self._cstruct("mds_se_fc_bwd_args", kwj)
+                    tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+                    self._keep.append(tab)
+                    vals.update(jobs=tab, njobs=len(v), max_rc=max(kwj["R"] * kwj["C"] for kwj in v))
+            elif isinstance(v, dict):
+                vals[k] = self._cstruct(v.get("_struct", "mds_pro_t"), v, resolve)
+            elif not resolve:
+                vals[k] = None if isinstance(v, (Lazy, P, torch.Tensor)) else v
+            elif not isinstance(v, (Lazy, P)):
+                vals[k] = v
             elif isinstance(v, Lazy) and v.kind == "input":
                 self._input_fields.append((struct_name, k))
-                v = 0
-            elif isinstance(v, (Lazy, P)):
-                t = v.resolve()
+                vals[k] = 0
+            else:
+                vals[k] = t = v.resolve()
                 self._keep.append(t)
-                v = t
-            vals[k] = v
         return cabi.make(struct_name, **vals)
 
     # ------------------------------------------------------------------ execution
@@ -1120,9 +1117,7 @@ class Plan:
         """hipEvent_t handles used as kernel STOP events (hipExtLaunchKernelGGL through mds_launch_event) + hipStreamWaitEvent"""
 
         def __init__(self, device, flags):
-            self.hip = C.CDLL(_hip_path())
-            self.hip.hipEventCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-            self.hip.hipStreamWaitEvent.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
+            self.hip = _hip()
             self.device, self.ev, self.flags = device, {}, flags
             # hipEventDisableTiming | hipEventDisableSystemFence: these events only order the second stream behind a kernel of
             # the chain - nobody on the host inspects them, so the system-scope fence (cache write-back for the host's benefit)
@@ -1215,11 +1210,7 @@ class Plan:
 
     def weight_tensors(self):
         """every tensor whose CONTENT the weight-dependent prefix of a forward reads (packed weights, eval BatchNorm table)"""
-        ts = [p for p, *_ in self.pack_jobs]
-        for e in self.eval_bn:
-            m = e.mod
-            ts += [m.weight, m.bias, m.running_mean, m.running_var]
-        return ts
+        return [p for p, *_ in self.pack_jobs] + [t for e in self.eval_bn for t in (e.mod.weight, e.mod.bias, e.mod.running_mean, e.mod.running_var)]
 
     def refresh_weights(self):
         """the weight-dependent prefix of a forward: the eval-mode BatchNorm table and the packed filter copies"""
@@ -1252,17 +1243,12 @@ class Plan:
             # autograd's saved-tensor checks and version-keyed caches (mds.predict) see the write
             torch.autograd.graph.increment_version(self._bn_buffers)
 
-    _hip = None
-
     def _memset(self, t):
         """zero a uint8 arena on the current stream: hipMemsetAsync (one runtime fill, also a node of a captured hipGraph)"""
         if t.device.type != "cuda" or not self.dev.hip_memset:
             t.zero_()
             return
-        if Plan._hip is None:
-            Plan._hip = C.CDLL(_hip_path())
-            Plan._hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
-        rc = Plan._hip.hipMemsetAsync(t.data_ptr(), 0, t.numel() * t.element_size(), self._stream())
+        rc = _hip().hipMemsetAsync(t.data_ptr(), 0, t.numel() * t.element_size(), self._stream())
         if rc != 0:
             raise RuntimeError(f"hipMemsetAsync failed: {rc}")
 
@@ -1270,7 +1256,5 @@ class Plan:
         self._memset(self._zero_bwd)
 
     def stale(self):
-        cur = tuple(p.data_ptr() for p, *_ in self.pack_jobs)
-        if self.eval_bn:
-            cur += tuple(t.data_ptr() for e in self.eval_bn for t in (e.mod.weight, e.mod.bias, e.mod.running_mean, e.mod.running_var))
-        return self.param_ptrs != cur
+        """a weight-dependent tensor was replaced (not written in place) since the plan took its address"""
+        return self.param_ptrs != tuple(t.data_ptr() for t in self.weight_tensors())
