@@ -877,6 +877,16 @@ extern "C" int mds_conv_wgrad(const mds_conv_wgrad_args* a, mds_stream_t stream)
   CONV_WGRAD_DIMS_OK(a);
   MDS_REQUIRE(a->x && a->dyt && a->dw, "conv_wgrad: null pointer");
   MDS_REQUIRE(a->pro.mode == MDS_PRO_NONE || (a->pro.scale && a->pro.shift), "conv_wgrad: prologue needs scale/shift");
+  // every block flushes all Cin * wtaps values of its output channels from an LDS staging that only the launch's taps fill: a filter
+  // slot that no tap names would add whatever the staging held, and two taps that name one slot would overwrite each other there
+  MDS_REQUIRE(a->wtaps >= 1 && a->wtaps <= MDS_MAX_TAPS, "conv_wgrad: wtaps=%d (1..%d)", a->wtaps, MDS_MAX_TAPS);
+  MDS_REQUIRE(a->ntaps == a->wtaps, "conv_wgrad: ntaps=%d taps for wtaps=%d filter slots: every filter slot takes exactly one tap", a->ntaps, a->wtaps);
+  unsigned named = 0;
+  for (int t = 0; t < a->ntaps; ++t) {
+    MDS_REQUIRE(a->wi[t] >= 0 && a->wi[t] < a->wtaps, "conv_wgrad: tap %d writes filter slot %d of %d", t, a->wi[t], a->wtaps);
+    named |= 1u << a->wi[t];
+  }
+  MDS_REQUIRE(named == (1u << a->wtaps) - 1u, "conv_wgrad: the tap list must name every one of the %d filter slots (a partial list: pass wtaps = its length)", a->wtaps);
   const long numel = (long)a->Cout * a->Cin * a->wtaps, slots = conv_wgrad_slots(a);
   MDS_REQUIRE(!a->partial.buf || slots > 0, "conv_wgrad: this build of k_c3.hip (C3_ABL) leaves slots unwritten: no partial buffer");
   MDS_PARTIAL_OK(a->partial, wg_floats(numel, slots > 0 ? slots : 0), "conv_wgrad");

@@ -360,7 +360,9 @@ int mds_conv_dgrad_post_ok(int dtype, int N, int IH, int IW, int Cin, int Cout, 
 
 /* weight gradient of the 3x3 convolution (forward geometry: is = stride, os = 1):
  * dw[co][ci][tap] += sum_{n,a,b} dy[n][a][b][co] * pro(x)[n][a*is+dy[t]][b*is+dx[t]][ci]
- * written in PyTorch OIHW order (dw[(co*Cin+ci)*wtaps + wi[t]]).                                */
+ * written in PyTorch OIHW order (dw[(co*Cin+ci)*wtaps + wi[t]]).  The tap list names every filter
+ * slot 0 .. wtaps-1 exactly once (ntaps == wtaps <= MDS_MAX_TAPS): a list that leaves a slot out, or
+ * names one twice, is refused.                                                                      */
 typedef struct {
   int dtype;
   int N, IH, IW, Cin, OH, OW, Cout;

@@ -32,6 +32,12 @@ _INT_VIEW = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 _GUARD_FLOOR = 4096
 _GUARD_CAP = 1 << 20
 _PATTERN = {}                    # (dtype, "t" | "out") -> the guard fill's bit pattern as an integer of the element's size
+# Every kernel instantiation ('conv_wgrad_kernel<float, 0, 2, 4, 9>') that a successful Backend.call() / Backend.rc() launched on
+# the simulator in this process: the launches that ran on guarded buffers from a kernel test.  Launches a Plan issues (module,
+# predictor, train-ops tests) do not pass through call() and are not in it - a whole-model comparison does not pin one variant.
+# Kept by the simulator apart from its launch record, so reset_launches(), knobs() and the record's 65,536-entry cap leave it
+# alone.  tests/test_zz_kernel_census.py compares it with the compiled kernels.
+KERNEL_TEST_INSTANTIATIONS = set()
 
 
 def guard_bytes(payload_bytes):
@@ -188,16 +194,52 @@ class Backend:
         be a guarded buffer - a test cannot hand an unguarded tensor to a launch"""
         for tensor in getattr(args, "_keep", ()):
             self._guarded_ptr(tensor)
+        self._inst_begin()
         self.lib.call(op, args, self.stream())      # raises when the launcher refuses: nothing was launched then
+        self._inst_collect()
         self._launched = True
 
     def rc(self, op, args):
         """call() for tests of the refusals: the entry point's return code instead of an exception"""
         for tensor in getattr(args, "_keep", ()):
             self._guarded_ptr(tensor)
+        self._inst_begin()
         code = self.lib.fn[op](ctypes.byref(args), self.stream())
+        if code == 0:
+            self._inst_collect()
         self._launched = self._launched or code == 0
         return code
+
+    def call_raw(self, op, jobs, *args):
+        """call() for the entry points that take a device-resident job table and counts instead of an argument struct
+        (mds_pack_weights, mds_bn_eval_table).  jobs: the host struct or ctypes array of structs; every pointer field of every job
+        must be null or an address inside a guarded buffer - checked here, as call() checks its tensors.  The table is copied into a
+        guarded buffer of its own; the stream is appended to `args`."""
+        for j, job in enumerate(jobs if isinstance(jobs, ctypes.Array) else [jobs]):
+            for name, ctype in job._fields_:
+                addr = getattr(job, name) if ctype is ctypes.c_void_p else None
+                if addr:
+                    rec = next((r for r in self._known.values() if r.view() is not None and r.lo <= addr < r.hi), None)
+                    if rec is None:
+                        raise AssertionError(f"job {j}: field '{name}' is no address inside a guarded buffer: allocate it with be.t() / be.out() and pass be.ptr()")
+                    if not any(r is rec for r, _ in self._pending):
+                        self._pending.append((rec, rec.view()))
+        table = self.t(torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8))
+        self._inst_begin()
+        self.lib.check(self.lib.fn[op](self._guarded_ptr(table), *args, self.stream()), op)
+        self._inst_collect()
+        self._launched = True
+
+    def _inst_begin(self):
+        if self.name == "emu":
+            from hipemu.loader import inst_begin
+            inst_begin()
+
+    def _inst_collect(self):
+        """simulator only: what the successful call just launched joins KERNEL_TEST_INSTANTIATIONS"""
+        if self.name == "emu":
+            from hipemu.loader import inst_seen
+            KERNEL_TEST_INSTANTIATIONS.update(inst_seen())
 
     def sync(self):
         """synchronise, then compare every guard registered (or launched on) since the last verification with its pattern"""

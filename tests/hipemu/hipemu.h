@@ -18,7 +18,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
+#include <typeinfo>
 #include <vector>
+#include <cxxabi.h>
 
 struct dim3 {
   unsigned x, y, z;
@@ -198,17 +201,55 @@ inline void run_block(BlockState& b) {
   g_blk = nullptr;
 }
 
-// Launch record: what MDS_LAUNCH was asked to run since the last reset (kernel expression as written at the call site, grid,
-// block.x), so that a test which forces a launch geometry through a developer knob can assert that it got it.  Read from Python
-// through the three hipemu_launch_* exports below (libmds_emu.so only - not part of include/mds.h).  Bounded: launches past
-// kLaunchCap are run but not remembered.
-struct LaunchRec { const char* kernel; unsigned gx, gy, gz, bx; };
+// Launch record: what MDS_LAUNCH was asked to run since the last reset (kernel expression as written at the call site, the
+// kernel INSTANTIATION it named - template values spelled out, as `nm -C` prints the compiled symbol - grid, block.x), so that a
+// test which forces a launch geometry through a developer knob can assert that it got it.  Read from Python through the
+// hipemu_launch_* exports below (libmds_emu.so only - not part of include/mds.h).  Bounded: launches past kLaunchCap are run but
+// not remembered.
+struct LaunchRec { const char* kernel; const char* inst; unsigned gx, gy, gz, bx; };
 inline std::vector<LaunchRec> g_launches;
 static const size_t kLaunchCap = 1 << 16;
+// The instantiations launched since hipemu_inst_begin(), each once, in first-launch order.  Independent of the record above:
+// neither hipemu_launch_reset() nor kLaunchCap touches it (tests/backends.py's census of what the kernel tests ran).
+inline std::vector<const char*> g_inst_seen;
 
-inline void launch(const char* kernel, dim3 grid, dim3 block, size_t smem, std::function<void()> body) {
+// The name of the kernel instantiation behind a function pointer that is a constant expression: typeid of a tag type that
+// carries the pointer as a template argument, demangled ("hipemu::KTag<&conv_wgrad_kernel<float, 0, 2, 4, 9>(mds_conv_args, ...)>"
+// or, for a non-template kernel, "hipemu::KTag<&aug_kernel(mds_aug_args)>"), cut down to "conv_wgrad_kernel<float, 0, 2, 4, 9>".
+// (__PRETTY_FUNCTION__ prints the template NAME for such an argument, without its values.)  One string per instantiation for the
+// life of the library, so records compare and store the pointer.
+template <auto K> struct KTag {};
+inline std::string inst_from_tag(const char* mangled) {
+  int status = 0;
+  char* d = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+  std::string s = (status == 0 && d) ? d : mangled;
+  free(d);
+  size_t a = s.find('&');
+  if (a == std::string::npos) return s;
+  s = s.substr(a + 1);
+  if (!s.empty() && s[0] == '(') s = s.substr(1);
+  if (s.compare(0, 5, "void ") == 0) s = s.substr(5);
+  static const char anon[] = "(anonymous namespace)::";      // k_pwk8.hip's kernels; nm prints it in front of __device_stub__, outside the name
+  if (s.compare(0, sizeof(anon) - 1, anon) == 0) s = s.substr(sizeof(anon) - 1);
+  int depth = 0;     // the name ends at the argument list: the first '(' outside template brackets
+  for (size_t i = 0; i < s.size(); ++i) {
+    if (s[i] == '<') ++depth;
+    else if (s[i] == '>') --depth;
+    else if (s[i] == '(' && depth == 0) return s.substr(0, i);
+  }
+  return s;
+}
+template <auto K> inline const char* inst_name() {
+  static const std::string s = inst_from_tag(typeid(KTag<K>).name());
+  return s.c_str();
+}
+
+inline void launch(const char* kernel, const char* inst, dim3 grid, dim3 block, size_t smem, std::function<void()> body) {
   static BlockState b;
-  if (g_launches.size() < kLaunchCap) g_launches.push_back({kernel, grid.x, grid.y, grid.z, block.x});
+  if (g_launches.size() < kLaunchCap) g_launches.push_back({kernel, inst, grid.x, grid.y, grid.z, block.x});
+  bool seen = false;
+  for (const char* p : g_inst_seen) seen = seen || p == inst;
+  if (!seen) g_inst_seen.push_back(inst);
   int n = block.x * block.y * block.z;
   if ((int)b.fibers.size() < n) {
     size_t old = b.fibers.size();
@@ -263,6 +304,17 @@ __attribute__((used, visibility("default"))) inline const char* hipemu_launch_ge
   const hipemu::LaunchRec& r = hipemu::g_launches[i];
   dims[0] = r.gx; dims[1] = r.gy; dims[2] = r.gz; dims[3] = r.bx;
   return r.kernel;
+}
+// entry i's instantiation name (NULL when i is out of range)
+__attribute__((used, visibility("default"))) inline const char* hipemu_launch_inst(int i) {
+  if (i < 0 || (size_t)i >= hipemu::g_launches.size()) return nullptr;
+  return hipemu::g_launches[i].inst;
+}
+// the instantiations launched since the last hipemu_inst_begin(): untouched by hipemu_launch_reset() and by the record's cap
+__attribute__((used, visibility("default"))) inline void hipemu_inst_begin() { hipemu::g_inst_seen.clear(); }
+__attribute__((used, visibility("default"))) inline int hipemu_inst_count() { return (int)hipemu::g_inst_seen.size(); }
+__attribute__((used, visibility("default"))) inline const char* hipemu_inst_get(int i) {
+  return (i < 0 || (size_t)i >= hipemu::g_inst_seen.size()) ? nullptr : hipemu::g_inst_seen[i];
 }
 }
 

@@ -53,7 +53,7 @@ MDS_DEV void mds_wait_stores() {}
 #define MDS_UNIFORM(x) (x)
 #define MDS_DYN_SMEM(name) char* name = hipemu::dyn_smem()
 #define MDS_LAUNCH(kernel, grid, block, smem, stream, ...) \
-  hipemu::launch(#kernel, grid, block, smem, [=]() { kernel(__VA_ARGS__); })
+  hipemu::launch(#kernel, hipemu::inst_name<&kernel>(), grid, block, smem, [=]() { kernel(__VA_ARGS__); })
 
 MDS_DEV u16x4 lds_tr4(const bf16_t* p) {
   const int lane = hipemu::lane_id();

@@ -313,7 +313,7 @@ def test_c3t_stride2_data_gradient(be, N, H, W, Cin, Cout, blocks):
 @pytest.mark.parametrize("stride,N,H,W,blocks,masked,Cin,Cout", [(1, 2, 14, 64, 0, True, 32, 128), (1, 1, 21, 45, 2, False, 32, 128), (2, 2, 12, 64, 0, True, 32, 128),
                                                                   (2, 1, 22, 40, 2, False, 32, 128), (1, 2, 9, 128, 0, "silu", 32, 16), (1, 1, 20, 70, 2, "silu", 32, 16),
                                                                   (2, 1, 10, 128, 0, "silu", 16, 64), (2, 2, 6, 64, 2, "silu", 32, 128)])
-def test_c3_post_statistics(be, stride, N, H, W, blocks, masked, Cin, Cout):
+def test_c3_post_statistics(be, stride, N, H, W, blocks, masked, Cin, Cout, with_res=None):
     """mds_poststat_t in k_c3.hip's data gradients (what engine._conv_dgrad asks for when mds_conv_dgrad_post_ok says 1): the
     output u is the gradient source of the BatchNorm below - sum g and sum g * xhat over all pixels with g = bf16(u) (x DropPath's
     per-image factor), next to the unchanged u; stride 1 = blocks.1.1's form (32 -> 128 forward, residual operand), stride 2 =
@@ -324,7 +324,9 @@ def test_c3_post_statistics(be, stride, N, H, W, blocks, masked, Cin, Cout):
     w = (torch.randn(Cout, Cin, 3, 3, generator=g) / (9 * Cin) ** 0.5).to(tdt)
     OH, OW, pt, pl = geo.conv_geometry(H, W, stride)
     dyt = torch.randn(N, Cout, OH, OW, generator=g).to(tdt)
-    res = torch.randn(N, H, W, Cin, generator=g).to(tdt) if (stride == 1 and Cout == 128) else None
+    if with_res is None:      # (the network's own forms; tests/test_k_instantiations.py asks for the others)
+        with_res = stride == 1 and Cout == 128
+    res = torch.randn(N, H, W, Cin, generator=g).to(tdt) if with_res else None
     yb = torch.randn(N, H, W, Cin, generator=g).to(tdt)
     bn = torch.stack([1 + 0.2 * torch.randn(Cin, generator=g), 0.3 * torch.randn(Cin, generator=g), 0.3 * torch.randn(Cin, generator=g), 0.5 + torch.rand(Cin, generator=g)])
     mask = torch.tensor([1.25, 0.0][:N]) if masked else None

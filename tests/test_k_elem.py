@@ -237,8 +237,7 @@ def test_se_forward_backward(be, dt, packed, C, RD):
     if packed:
         w2t = be.out((RD, C), torch.float32, float("nan"))
         job = cabi.make("mds_pack_job", src=w2d, dst=w2t, kind=cabi.MDS_PACK_IO_F32, O=C, I=RD, taps=1)
-        raw = be.t(torch.frombuffer(bytearray(bytes(job)), dtype=torch.uint8))
-        be.lib.check(be.lib.fn["pack_weights"](be.ptr(raw), 1, C * RD, code, be.stream()), "pack_weights")
+        be.call_raw("pack_weights", job, 1, C * RD, code)
         be.sync()
         assert torch.equal(w2t.cpu(), w2.t().contiguous())
     be.call("se_fc_fwd", cabi.make("mds_se_fc_fwd_args", groups=G, C=C, R=RD, pooled=pooled, w1=w1d, b1=b1d,
@@ -567,8 +566,7 @@ def test_pack_weights(be, dt):
     jobs = (Job * 4)()
     for j, (s, d, (k, O, I, t)) in enumerate(zip(srcs, dsts, kinds)):
         jobs[j].src = be.ptr(s); jobs[j].dst = be.ptr(d); jobs[j].kind = k; jobs[j].O = O; jobs[j].I = I; jobs[j].taps = t
-    raw = be.t(torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8))
-    be.lib.check(be.lib.fn["pack_weights"](be.ptr(raw), 4, 20 * 12 * 9, code, be.stream()), "pack_weights")
+    be.call_raw("pack_weights", jobs, 4, 20 * 12 * 9, code)
     be.sync()
     assert_close(dsts[0].view(20, 9, 12), w3.view(20, 12, 9).permute(0, 2, 1), dt)
     assert_close(dsts[1].view(12, 9, 20), w3.view(20, 12, 9).flip(2).permute(1, 2, 0), dt)
@@ -591,8 +589,7 @@ def test_pack_weights_transposed(be, dt, O, I):
     jobs = (Job * 2)()
     for j, (d, k) in enumerate(((d_flip, cabi.MDS_PACK_IO_FLIP), (d_f32, cabi.MDS_PACK_IO_F32))):
         jobs[j].src = be.ptr(src); jobs[j].dst = be.ptr(d); jobs[j].kind = k; jobs[j].O = O; jobs[j].I = I; jobs[j].taps = 1
-    raw = be.t(torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8))
-    be.lib.check(be.lib.fn["pack_weights"](be.ptr(raw), 2, O * I, code, be.stream()), "pack_weights")
+    be.call_raw("pack_weights", jobs, 2, O * I, code)
     be.sync()
     assert_close(d_flip.view(I, O), w.t(), dt)
     assert torch.equal(d_f32.view(I, O).cpu(), w.t().contiguous())

@@ -428,8 +428,7 @@ def _frag_pack(be, w, io=False):
     job.src, job.dst = be.ptr(src), be.ptr(dst)
     job.kind = cabi.MDS_PACK_FRAG_IO if io else cabi.MDS_PACK_FRAG_OI
     job.O, job.I, job.taps = (K, N, 1) if io else (N, K, 1)
-    tab = be.t(torch.frombuffer(bytearray(bytes(job)), dtype=torch.uint8))
-    be.lib.check(be.lib.fn["pack_weights"](be.ptr(tab), 1, dst.numel(), cabi.MDS_BF16, be.stream()), "pack_weights")
+    be.call_raw("pack_weights", job, 1, dst.numel(), cabi.MDS_BF16)
     be.sync()
     return dst
 
